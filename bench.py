@@ -21,10 +21,20 @@ Data are synthetic: weights random with the trained structure, 6000-node-class
 reservoirs (n = 5760/6160/6048/5880), a seeded T30L8 analysis state, synthetic
 boundary fields for the physics.  fp64 arithmetic throughout; reservoir weights
 held at their fp32 file precision (exact).  The reservoir side alone (configs[1])
-is reported beside the headline as `reservoir_only`.
+is reported beside the headline as `reservoir_only` (--full).
 
-Usage: python bench.py [--gpus N --steps K --warmup W]
+Usage: python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR]
        python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...
+
+A plain run does what the headline needs and no more: setup, the warmup steps, the K
+timed steps, the result line (the readout / update roofline in it comes from those
+same K steps).  --full adds every supplementary measurement, each a run of its own:
+the K steps again without the run_speedy poll, the forcing's recompute cost, the
+reservoir-only leg (configs[1]), the SPEEDY-step leg with its phase roofline, the
+W_out-training leg and the CPU baseline; their keys are null in a plain line.
+--dump-outputs DIR writes what the last timed step left for its caller (the loop's
+outvecs, assembled grids, forecast and next inputs) as DIR/<name>.npy, fp64; the
+inputs are seeded, so two builds run with the same arguments compare array by array.
 
 `python bench.py --gpus N` (N > 1, WORLD_SIZE unset) launches its N ranks itself:
 the parent starts N fresh child processes of this script, one per GPU, with RANK /
@@ -62,6 +72,12 @@ def parse():
     p.add_argument("--steps", type=int, default=300)
     p.add_argument("--warmup", type=int, default=20)
     p.add_argument("--regions", type=int, default=1152)
+    p.add_argument("--full", action="store_true",
+                   help="also run the supplementary measurements (poll cost, forcing recompute cost, reservoir-only, "
+                        "SPEEDY-step, training legs, CPU baseline); off: the timed steps and the result line only")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write the arrays the last timed step left for its caller (fb, lm, ov, "
+                        "g4, g2, pr, f4, f2: 10 MB) as DIR/<name>.npy in float64 (rank 0)")
     p.add_argument("--weights", choices=("f32", "f64"), default="f32")
     p.add_argument("--cpu-threads", type=int,
                    default=len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else os.cpu_count(),
@@ -408,9 +424,16 @@ def main():
     dt = timed(step_polled if poll else step, args.steps, timing=True)
     upd_ms, rd_ms = res.kernel_times()
     steps_done = ran[0]
+    if args.dump_outputs and rank == 0:
+        # the last timed step's results, before anything else touches the loop's buffers
+        # (timed() drained the loop; a pipelined begin in flight writes none of these)
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, a in (("fb", fb), ("lm", lm), ("ov", ov), ("g4", g4), ("g2", g2), ("pr", pr), ("f4", f4),
+                        ("f2", f2)):
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), a.cpu().numpy().astype(np.float64, copy=False))
     n_ford = dyn.fordate_count() - n_ford0
     # the poll's cost: the same K steps again without the host waiting on run_speedy
-    dt_nopoll = timed(step, args.steps) if poll and not ended else None
+    dt_nopoll = timed(step, args.steps) if args.full and poll and not ended else None
     if args.pipelined and args.overlap:  # the next step's begin is in flight: close it (untimed)
         res.predict_finish(lm, ov, stream=loop.main)
         torch.cuda.synchronize()
@@ -450,7 +473,7 @@ def main():
 
     # supplementary: the reservoir side alone (configs[1]), SPEEDY's step alone
     reservoir_only = None
-    if args.reservoir_steps > 0:
+    if args.full and args.reservoir_steps > 0:
         res.set_update_cus(0)  # this leg runs on the whole device: one balanced-update block per CU of all 256
 
         def rstep():
@@ -481,18 +504,9 @@ def main():
             "roofline_unpaced": unpaced}
     date_forcing = {"on": False}
     if args.date_forcing:
-        # the forcing's own cost: forced recomputations (the coupler at a date + hybrid SST
-        # + fordate: one grid-point kernel and spec of tcorh / qcorh), on one stream
-        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        for i in range(3):
-            dyn.fordate(1982, 1 + i % 12, 1 + i % 28, force=True)
-        ev0.record()
-        nrep = 50
-        for i in range(nrep):
-            dyn.fordate(1982, 1 + i % 12, 1 + i % 28, force=True)
-        ev1.record()
-        torch.cuda.synchronize()
-        f_ms = ev0.elapsed_time(ev1) / nrep
+        f_ms = None
+        if args.full:
+            f_ms = forcing_recompute_ms(dyn)
         date_forcing = {
             "on": True,
             "calendar": "startyear 1981, hours_base 8760 (1982-01-01), 6 h per step: each window's date as "
@@ -501,14 +515,14 @@ def main():
             "note": "recomputed when the date (once a day: every 4th step) or the slab's hybrid SST changed; "
                     "on SPEEDY's stream behind the previous window (beside the finish and assembly), or, on a "
                     "step with a new hybrid SST, behind that SST on the reservoir stream before the grid hop",
-            "recompute_ms": round(f_ms, 4),
-            "per_step_ms": round(f_ms * n_ford / max(steps_done, 1), 4)}
+            "recompute_ms": round(f_ms, 4) if f_ms is not None else None,
+            "per_step_ms": round(f_ms * n_ford / max(steps_done, 1), 4) if f_ms is not None else None}
     dyn.close()
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and args.cpu_threads > 0:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and args.cpu_threads > 0:
         cpu = cpu_baseline(nreg, mask, args.cpu_threads)
-    speedy = speedy_leg(dev, world, rank, args) if args.speedy_steps > 0 else None
-    training = training_leg(dev, mask, args, world, rank) if args.train_regions > 0 else None
+    speedy = speedy_leg(dev, world, rank, args) if args.full and args.speedy_steps > 0 else None
+    training = training_leg(dev, mask, args, world, rank) if args.full and args.train_regions > 0 else None
 
     if rank == 0:
         steps_per_s = steps_done / dt
@@ -519,6 +533,7 @@ def main():
             "n_gpus": world,
             "steps": args.steps,
             "warmup": args.warmup,
+            "full": bool(args.full),
             "ms_per_step": round(dt / steps_done * 1e3, 4),
             "higher_is_better": True,
             "scaling": "strong",
@@ -606,6 +621,22 @@ def main():
         comm.close()
     if world > 1:
         dist.destroy_process_group()
+
+
+def forcing_recompute_ms(dyn, nrep=50):
+    """The forcing's own cost: forced recomputations (the coupler at a date + hybrid SST
+    + fordate: one grid-point kernel and spec of tcorh / qcorh), on one stream."""
+    import torch
+
+    ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    for i in range(3):
+        dyn.fordate(1982, 1 + i % 12, 1 + i % 28, force=True)
+    ev0.record()
+    for i in range(nrep):
+        dyn.fordate(1982, 1 + i % 12, 1 + i % 28, force=True)
+    ev1.record()
+    torch.cuda.synchronize()
+    return ev0.elapsed_time(ev1) / nrep
 
 
 F64_VALU_PEAK_TF = 78.6  # MI355X fp64 vector (256 CUs x 4 SIMDs x 64 lanes x 2 flop / 4 clk x 2.4 GHz)
@@ -947,6 +978,10 @@ def cpu_baseline(nreg: int, mask, threads: int):
     (reported beside it); no sample is extrapolated."""
     import subprocess
 
+    ref_dyn = os.path.join(REPO, "oracle", "_ref", "libspeedy_ref_dyn.so")
+    if not os.path.exists(ref_dyn):  # built by `make -C oracle ref` where the reference's sources are present
+        log(0, f"cpu_baseline skipped: {os.path.relpath(ref_dyn, REPO)} is not built (its window leg needs it)")
+        return None
     sys.path.insert(0, os.path.join(REPO, "oracle"))
     import oracle
     from speedy_ml_amd.synthetic import feedback_vector, initial_state, local_model_vector, region_weights

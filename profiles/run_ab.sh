@@ -4,7 +4,7 @@
 set -o pipefail
 mkdir -p gpurun_out
 N=${N:-3}
-B="python -u bench.py --no-cpu-baseline --train-regions 0 --reservoir-steps 0"
+B="python -u bench.py --full --no-cpu-baseline --train-regions 0 --reservoir-steps 0"
 for i in $(seq 1 $N); do
   for v in A B; do
     if [ $v = A ]; then export SML_LIB=$SML_LIB_A; else unset SML_LIB; fi

@@ -91,7 +91,7 @@ def main():
     except Exception:
         pass
     lines = [f"# rocprofv3 summary, round {rnd}", "",
-             "Command: `rocprofv3 --kernel-trace --stats -- python3 bench.py --steps 20 --warmup 3 "
+             "Command: `rocprofv3 --kernel-trace --stats -- python3 bench.py --full --steps 20 --warmup 3 "
              "--no-cpu-baseline --train-regions 0 --speedy-steps 8 --reservoir-steps 10` (1 x MI355X), then one `--pmc FETCH_SIZE` and one `--pmc WRITE_SIZE` pass "
              f"of the same command.  Source commit: {commit or 'n/a'}.", "",
              "| kernel | calls | avg us | % time | FETCH_SIZE KiB/launch (raw) | WRITE_SIZE KiB/launch |",

@@ -33,6 +33,17 @@ def test_launcher_gives_every_rank_its_environment():
     assert len({o["rank"]["pid"] for o in others} | {me["pid"]}) == 3  # three processes
 
 
+def test_launcher_passes_full_and_dump_outputs_to_its_ranks(tmp_path):
+    """--full (the supplementary legs) and --dump-outputs DIR are options of every rank's
+    command line; the dry run stops before the GPU, so it writes nothing."""
+    p = _run("--gpus", "2", "--steps", "3", "--warmup", "1", "--full", "--dump-outputs", str(tmp_path / "dump"),
+             "--dry-run", "env")
+    assert p.returncode == 0, p.stderr[-2000:]
+    lines = [json.loads(x) for x in p.stdout.splitlines() if x.startswith("{")]
+    assert len(lines) == 1 and lines[0]["rank"]["WORLD_SIZE"] == "2"
+    assert not (tmp_path / "dump").exists()
+
+
 def test_launcher_ranks_join_one_gloo_group():
     p = _run("--gpus", "4", "--dry-run", "gloo")
     assert p.returncode == 0, p.stderr[-2000:]

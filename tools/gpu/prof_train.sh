@@ -3,7 +3,7 @@ set -o pipefail
 cd "$GRAFT_REPO_ROOT"; tag=$1; o=$GRAFT_REPO_ROOT/gpurun_out/$tag; mkdir -p $o
 export TMPDIR=/tmp
 for kv in $2; do export $kv; done
-(cd /tmp && timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $o/prof -o run --output-format csv -- python3 -u $GRAFT_REPO_ROOT/bench.py --no-cpu-baseline --reservoir-steps 0 --speedy-steps 0 --steps 2 --warmup 1) > $o/b.json 2> $o/b.err || { tail $o/b.err; exit 1; }
+(cd /tmp && timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $o/prof -o run --output-format csv -- python3 -u $OLDPWD/bench.py --full --no-cpu-baseline --reservoir-steps 0 --speedy-steps 0 --steps 2 --warmup 1) > $o/b.json 2> $o/b.err || { tail $o/b.err; exit 1; }
 python3 - $o <<'PY'
 import csv, sys, collections
 o = sys.argv[1]

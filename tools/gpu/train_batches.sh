@@ -1,6 +1,6 @@
 set -o pipefail
 cd "$GRAFT_REPO_ROOT"; o=gpurun_out/r06tb; mkdir -p $o
-B="bench.py --no-cpu-baseline --reservoir-steps 0 --speedy-steps 0 --steps 2 --warmup 1"
+B="bench.py --full --no-cpu-baseline --reservoir-steps 0 --speedy-steps 0 --steps 2 --warmup 1"
 for rep in 1 2; do
  for cfg in "SML_LIB=abx/g16/speedy-ml-1_amd/lib/libspeedyml.so:4" "SML_LIB=abx/g16/speedy-ml-1_amd/lib/libspeedyml.so:1" "SML_AB=m4:1" "SML_LIB=abx/g16/speedy-ml-1_amd/lib/libspeedyml.so:2"; do
   e=${cfg%%:*}; nb=${cfg##*:}; f=$o/$(echo $e | tr -c 'a-z0-9' _)_${nb}_$rep
