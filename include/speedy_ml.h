@@ -210,11 +210,14 @@ int sml_res_set_read_waves(sml_reservoirs *c, int waves);
  * read from their CSR copies (SML_RES_PATH_CSR; before any region is loaded), the
  * state update one block per (region, part) instead of the balanced persistent grid
  * (SML_RES_PATH_PER_REGION), the v_p finish one thread per output instead of in
- * column groups (SML_RES_PATH_UNGROUPED_FINISH).  For tests and for a host bisecting a
+ * column groups (SML_RES_PATH_UNGROUPED_FINISH), the training drive one update launch
+ * per column after a column-writer launch instead of one persistent launch per batch
+ * (SML_RES_PATH_STEPWISE_DRIVE).  For tests and for a host bisecting a
  * difference; 0 restores the defaults. */
 #define SML_RES_PATH_CSR 1
 #define SML_RES_PATH_PER_REGION 2
 #define SML_RES_PATH_UNGROUPED_FINISH 4
+#define SML_RES_PATH_STEPWISE_DRIVE 8
 int sml_res_set_reference_paths(sml_reservoirs *c, int flags);
 /* the number of CUs the context's launches get (its stream's CU mask; 0 = the whole
  * device): the balanced state update runs one block per CU over equal shares of all
@@ -251,6 +254,33 @@ int sml_res_synchronize(sml_reservoirs *c, const double *d_inputs, int length, i
  * forecast (sml_res_tile_local_model or the hybrid loop's start). */
 int sml_res_start_prediction(sml_reservoirs *c, const double *d_inputs, int length, int64_t stride,
                              double *d_feedback, void *stream);
+/* The training drive: reservoir_layer_chunking_hybrid (src/mod_reservoir.f90:1065-1173)
+ * with the first lines of chunking_matmul (:1662-1675) -- what sml_train_accumulate
+ * consumes -- for one batch of m columns and every local region, "record, then advance".
+ * For column c = 0 .. m-1, with u_c the region's part of input block c
+ * (d_inputs + c * stride, the packed feedback layout; stride as sml_res_synchronize):
+ *   rows ncs .. ncs+n-1 of column c of the region's state block = the current state x
+ *     with every 0-based odd node squared (states(2:n:2,:)**2, :1133);
+ *   rows 0 .. ncs-1 = the region's ncs values of model block c (d_model +
+ *     c * model_stride, laid out [nlocal][ncs] like d_local_model; model_stride >=
+ *     nlocal * ncs; d_model is ignored and may be NULL when chunk_speedy == 0);
+ *   column c of the region's target block = the nout target entries of u_c
+ *     (tile_full_input_to_target_data2d, res_domain.f90:602-651; sml_region_target_index);
+ *   then x = (1-leak) x + leak tanh(A x + W_in u_c), bitwise sml_res_synchronize's update.
+ * d_states: the layout sml_train_accumulate reads -- regions back to back, region i's
+ * block (ncs + n_i) x m column-major, starting at m * sum_{j<i} (ncs + n_j).
+ * d_targets: per region nout x m column-major, back to back; NULL skips it; non-NULL
+ * on a sml_res_create_generic context (no geometry) is SML_ERR_ARG.
+ * The discard phase is sml_res_synchronize over the first blocks from x = 0; batch b
+ * is then one call on the next m blocks.  Every batch advances from the unsquared
+ * state (the reference's ML-only form restarts from the squared column, :1032: a
+ * deliberate difference), and the last batch ends with one advance the reference
+ * does not make.  m == 0 is a no-op.  Stream-ordered, no host synchronisation.
+ * One launch per batch, a workgroup per region with the state in LDS; with
+ * SML_RES_PATH_STEPWISE_DRIVE, or where a region's two states + two inputs exceed the
+ * device's LDS per workgroup, m launches of the update. */
+int sml_res_train_drive(sml_reservoirs *c, const double *d_inputs, int m, int64_t stride, const double *d_model,
+                        int64_t model_stride, double *d_states, double *d_targets, void *stream);
 /* host convenience: H2D, step, D2H (synchronous) */
 int sml_res_step_host(sml_reservoirs *c, const double *feedback, const double *local_model, double *outvec);
 /* bytes of weights + state resident on the device (for roofline bookkeeping) */
@@ -737,6 +767,14 @@ int sml_copy_to_host(void *dst, const void *d_src, int64_t bytes);
  * src/res_domain.f90:123-204), 1-based: g[12] = res_xstart, res_xend, res_ystart,
  * res_yend, resx, resy, in_xstart, in_xend, in_ystart, in_yend, inx, iny */
 int sml_region_geometry(int numregions, int region, int *g);
+/* the 0-based positions of a region's training targets inside its feedback vector
+ * [atmo(4,inx,iny,8) | logp(inx,iny) | precip(inx,iny) | sst? | tisr]
+ * (tile_full_input_to_target_data2d, src/res_domain.f90:602-651): atmo (v, x, y, z) for
+ * x, y in the tdata ranges of get_trainingdataindices (:547-574; the polar tiles
+ * differ), z = 1..8, in Fortran order with v fastest, then logp (x, y), then precip
+ * (x, y).  idx holds 34 * resx * resy entries (136 at 1152 regions); *count receives
+ * that number.  sst (0 / 1) is the region's flag; its block follows the targets. */
+int sml_region_target_index(int numregions, int region, int sst, int32_t *idx, int *count);
 /* processor_decomposition (src/res_domain.f90:31-62): 0-based regions of rank irank */
 int sml_processor_decomposition(int numregions, int numprocs, int irank, int *regions, int *count);
 /* the mean / std (36 each) local region i was loaded with (host copies) */

@@ -1429,6 +1429,19 @@ extern "C" int sml_region_geometry(int numregions, int region, int *g) {
     return SML_OK;
 }
 
+// the training targets' 0-based positions inside the region's feedback vector
+// (region_target_index, csrc/sml_internal.hpp): idx holds 34 resx resy entries, 136 at
+// 1152 regions.  The sst block sits after precip, so the flag moves none of them.
+extern "C" int sml_region_target_index(int numregions, int region, int sst, int32_t *idx, int *count) {
+    SML_REQUIRE(idx && count, "null argument");
+    (void)sst;
+    RegionGeom r;
+    SML_REQUIRE(region_geom(numregions, region, &r), "region %d of %d does not decompose the grid", region,
+                numregions);
+    *count = region_target_index(r, idx);
+    return SML_OK;
+}
+
 // processor_decomposition (res_domain.f90:31-62): the regions (0-based) rank irank of
 // numprocs owns; returns their count in *count (regions may be NULL to ask only)
 extern "C" int sml_processor_decomposition(int numregions, int numprocs, int irank, int *regions, int *count) {

@@ -128,6 +128,31 @@ inline int region_ninp(const RegionGeom &g, bool sst) {
     return kVars * in2d * kZGrid + in2d + in2d + (sst ? in2d : 0) + in2d;
 }
 
+// the training targets inside a region's feedback vector (0-based positions):
+// tile_full_input_to_target_data2d (res_domain.f90:602-651) cuts the region's own
+// points out of the overlap tile -- atmo (v, x, y, z) over the tdata_x / tdata_y ranges
+// of get_trainingdataindices (:547-574; a polar tile has no overlap row on its pole
+// side), v fastest, then logp (x, y), then precip (x, y).  Returns their count.
+inline int region_target_index(const RegionGeom &g, int32_t *idx, int overlap = 1) {
+    const int xs = 1 + overlap, xe = g.inx - overlap;
+    int ys = 1 + overlap, ye = g.iny - overlap;
+    if (g.res_ystart - overlap < 1) {
+        ys = 1 + (g.res_ystart - 1);
+    } else if (g.res_yend + overlap > kYGrid) {
+        ye = g.iny - (kYGrid - g.res_yend);
+    }
+    const int in2d = g.inx * g.iny, natmo = kVars * in2d * kZGrid;
+    int c = 0;
+    for (int z = 0; z < kZGrid; ++z)
+        for (int y = ys; y <= ye; ++y)
+            for (int x = xs; x <= xe; ++x)
+                for (int v = 0; v < kVars; ++v) idx[c++] = v + kVars * ((x - 1) + g.inx * ((y - 1) + g.iny * z));
+    for (int blk = 0; blk < 2; ++blk)  // logp, precip
+        for (int y = ys; y <= ye; ++y)
+            for (int x = xs; x <= xe; ++x) idx[c++] = natmo + blk * in2d + (x - 1) + g.inx * (y - 1);
+    return c;
+}
+
 // processor_decomposition (res_domain.f90:31-62): the regions rank irank of numprocs
 // owns -- a contiguous block of numregions/numprocs, and for ranks 1..left one of the
 // `left` leftover regions at the end (0-based region numbers)

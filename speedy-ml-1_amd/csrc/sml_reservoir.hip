@@ -140,6 +140,11 @@ struct sml_reservoirs {
     // the v_p finish one thread per output (vp_sum) instead of in column groups: the
     // fallback when ncs does not fit the groups, or forced (sml_res_set_reference_paths)
     bool finish_ungrouped = false;
+    // the training drive as m launches of the update, each after a column writer
+    // (k_drive_record), instead of k_res_drive: forced (sml_res_set_reference_paths), or
+    // taken where a region does not fit k_res_drive's LDS
+    bool stepwise_drive = false;
+    int32_t *d_tgt_idx = nullptr;  // [nlocal][nout] the targets' positions in each region's feedback
     // the next grid finish waits in-kernel for *fin_wflag >= fin_wval (sml::res_finish_wait)
     const uint64_t *fin_wflag = nullptr;
     uint64_t fin_wval = 0;
@@ -247,11 +252,21 @@ struct Pair<double> {
 };
 
 // pair p of row i (slots 2p, 2p + 1) from the pair-major ELL copy
-template <typename WT>
+// kNT = false: plain (cached) loads, for a reader that comes back to the same rows
+// (the training drive re-reads its region's A every column)
+template <bool kNT, typename T>
+__device__ inline T row_load(const T *p) {
+    if constexpr (kNT)
+        return stream_load(p);
+    else
+        return *p;
+}
+
+template <typename WT, bool kNT = true>
 __device__ inline void load_pair(RowRegs<WT> &q, int p, const uint32_t *cp, const WT *vp) {
     typedef typename Pair<WT>::N V2;
-    q.c[p] = stream_load(cp);
-    const V2 v = stream_load(reinterpret_cast<const V2 *>(vp));
+    q.c[p] = row_load<kNT>(cp);
+    const V2 v = row_load<kNT>(reinterpret_cast<const V2 *>(vp));
     q.v[2 * p] = v.x;
     q.v[2 * p + 1] = v.y;
 }
@@ -261,7 +276,7 @@ __device__ inline uint32_t win_col_implicit(const RegionDev &rg, int i) {
 }
 
 // every load of row i, branching on the region's widths (k_res_update, k_res_begin)
-template <typename WT>
+template <typename WT, bool kNT = true>
 __device__ inline void load_row(RowRegs<WT> &q, const RegionDev &rg, const Ell &ell, int i, bool live) {
     if (live && rg.a_w > 0) {
         const uint32_t *cb = reinterpret_cast<const uint32_t *>(ell.a_col + rg.a_ell);
@@ -269,15 +284,15 @@ __device__ inline void load_row(RowRegs<WT> &q, const RegionDev &rg, const Ell &
         const int np = (rg.a_w + 1) >> 1, n = rg.n;
 #pragma unroll
         for (int p = 0; p < kEllA / 2; ++p)
-            if (p < np) load_pair(q, p, cb + (size_t)p * n + i, vb + 2 * ((size_t)p * n + i));
+            if (p < np) load_pair<WT, kNT>(q, p, cb + (size_t)p * n + i, vb + 2 * ((size_t)p * n + i));
         if (rg.a_ov) {
-            q.om = stream_load(ell.a_om + rg.a_om + (i >> 6));
-            q.ob = stream_load(ell.a_ob + rg.a_om + (i >> 6));
+            q.om = row_load<kNT>(ell.a_om + rg.a_om + (i >> 6));
+            q.ob = row_load<kNT>(ell.a_ob + rg.a_om + (i >> 6));
         }
     }
     if (live && rg.w_w > 0) {
-        q.wc = rg.w_q > 0 ? win_col_implicit(rg, i) : (uint32_t)stream_load(ell.w_col + rg.w_ell + i);
-        q.wv = stream_load((const WT *)ell.w_val + rg.w_ell + i);
+        q.wc = rg.w_q > 0 ? win_col_implicit(rg, i) : (uint32_t)row_load<kNT>(ell.w_col + rg.w_ell + i);
+        q.wv = row_load<kNT>((const WT *)ell.w_val + rg.w_ell + i);
     }
 }
 
@@ -364,6 +379,49 @@ __device__ __attribute__((always_inline)) inline double ell_row_value(const RowR
     return (1.0 - leak) * xs[i] + leak * xn;
 }
 
+// the CSR copies of one region's A and W_in (rows past the ELL slots, a dense W_in)
+template <typename WT>
+struct CsrRows {
+    const int32_t *rp;
+    const uint16_t *ac;
+    const WT *av;
+    const int32_t *wp;
+    const uint16_t *wc;
+    const WT *wv;
+};
+
+// x_new(i) for a region of any form, from the row's ELL loads (load_row) where the
+// region has them and from the CSR copies otherwise: the row of update_block, shared
+// with the training drive (k_res_drive) so both give the same bits.  The overflow
+// entry, when the region has a list, is fetched here.
+template <typename WT>
+__device__ __attribute__((always_inline)) inline double row_value(RowRegs<WT> &cur, const RegionDev &rg,
+                                                                  const Ell &ell, const CsrRows<WT> &csr,
+                                                                  const double *xs, const double *fs, int i,
+                                                                  double leak) {
+    // y = A x, entries of row i in the file's order (COO semantics, duplicates add)
+    double y = 0.0;
+    if (rg.a_w > 0) {
+        cur.oh = false;
+        if (rg.a_ov) resolve_ovf<WT, false>(cur, rg, ell, i);
+#pragma unroll
+        for (int s = 0; s < kEllA; ++s)
+            if (s < rg.a_w) y = y + (double)cur.v[s] * xs[ell_col(cur, s)];
+        if (cur.oh) y = y + (double)cur.ov * xs[cur.oc];  // the row's last entry (ell_row_value)
+    } else {
+        for (int e = csr.rp[i], e1 = csr.rp[i + 1]; e < e1; ++e) y = y + (double)csr.av[e] * xs[csr.ac[e]];
+    }
+    // temp = W_in feedback
+    double t = 0.0;
+    if (rg.w_w > 0) {
+        t = t + (double)cur.wv * fs[cur.wc];
+    } else {
+        for (int e = csr.wp[i], e1 = csr.wp[i + 1]; e < e1; ++e) t = t + (double)csr.wv[e] * fs[csr.wc[e]];
+    }
+    const double xn = res_tanh(y + t);
+    return (1.0 - leak) * xs[i] + leak * xn;
+}
+
 // update: logical block = (region, part); a part is a contiguous range of rows
 // walked in passes of 1024 rows.  With kLds the region's state x and feedback u
 // are staged once per block in LDS and the SpMV's random column gathers hit LDS
@@ -399,41 +457,15 @@ __device__ __attribute__((always_inline)) inline void update_block(
         xs = sx;
         fs = sf;
     }
-    const int32_t *rp = a_rp + rg.a_rp;
-    const uint16_t *ac = a_col + rg.a_nz;
-    const WT *av = a_val + rg.a_nz;
-    const int32_t *wp = w_rp + rg.w_rp;
-    const uint16_t *wc = w_col + rg.w_nz;
-    const WT *wv = w_val + rg.w_nz;
+    const CsrRows<WT> csr{a_rp + rg.a_rp, a_col + rg.a_nz, a_val + rg.a_nz, w_rp + rg.w_rp, w_col + rg.w_nz,
+                          w_val + rg.w_nz};
     for (int base = beg; base < end; base += kThr) {
         const int i = base + tid;
         const bool live = i < end;
         const int inext = i + kThr;
         if (base + kThr < end) load_row(nxt, rg, ell, inext, inext < end);
-        if (live) {
-            // y = A x, entries of row i in the file's order (COO semantics, duplicates add)
-            double y = 0.0;
-            if (rg.a_w > 0) {
-                cur.oh = false;
-                if (rg.a_ov) resolve_ovf<WT, false>(cur, rg, ell, i);
-#pragma unroll
-                for (int s = 0; s < kEllA; ++s)
-                    if (s < rg.a_w) y = y + (double)cur.v[s] * xs[ell_col(cur, s)];
-                if (cur.oh) y = y + (double)cur.ov * xs[cur.oc];  // the row's last entry (ell_row_value)
-            } else {
-                for (int e = rp[i], e1 = rp[i + 1]; e < e1; ++e) y = y + (double)av[e] * xs[ac[e]];
-            }
-            // temp = W_in feedback
-            double t = 0.0;
-            if (rg.w_w > 0) {
-                t = t + (double)cur.wv * fs[cur.wc];
-            } else {
-                for (int e = wp[i], e1 = wp[i + 1]; e < e1; ++e) t = t + (double)wv[e] * fs[wc[e]];
-            }
-            const double xn = res_tanh(y + t);
-            const double xv = (1.0 - leak) * xs[i] + leak * xn;
-            x_new[rg.x + i] = xv;  // (x~ = x with x(2:n:2)**2: squared by the readout's loads, rd_x)
-        }
+        if (live)  // (x~ = x with x(2:n:2)**2: squared by the readout's loads, rd_x)
+            x_new[rg.x + i] = row_value(cur, rg, ell, csr, xs, fs, i, leak);
         cur = nxt;
     }
 }
@@ -457,6 +489,125 @@ __global__ __launch_bounds__(kUpdThreads, kMinW) void k_res_update(
             update_block<WT, kLds>(lb, smem, R, a_rp, a_col, a_val, w_rp, w_col, w_val, ell, x_old, x_new,
                                    feedback, leak, parts, lds_x);
         if (base + (int)gridDim.x < nlog) __syncthreads();  // the block's LDS, reused next round
+    }
+}
+
+// ------------------------------------------------------------------ training drive
+// reservoir_layer_chunking_hybrid (src/mod_reservoir.f90:1065-1173) with the first lines
+// of chunking_matmul (:1662-1675): the reservoirs driven by a batch of m inputs, every
+// state kept as one column of the W_out fit's augmented_states.  Column c of a region
+// is [model block c (ncs rows); x~ (n rows)] -- x~ the state BEFORE input c with its
+// 0-based odd nodes squared (states(2:n:2,:)**2, :1133) -- and column c of its targets
+// is the region's own points of input c (tile_full_input_to_target_data2d); then
+// x <- (1 - leak) x + leak tanh(A x + W_in u_c).  Region r's block starts at
+// m (row0[r] + r ncs) doubles: the layout sml_train_accumulate reads.
+//
+// Training is teacher-forced -- no exchange, no readout between steps -- so a region's
+// whole batch runs in one workgroup: k_res_drive, a block per region, keeps x and u in
+// LDS (two copies of each: the SpMV gathers random columns of the old state while the
+// new one is written, and input c + 1 lands while input c is read), one barrier per
+// column, one launch per batch.  The row is row_value, so the state is bitwise the one
+// sml_res_synchronize produces.  The first pass's A / W_in rows of the next column are
+// loaded before the barrier that ends the current one.  A block re-reads its region's
+// A and W_in every column, so it loads them cached (not the update's streaming loads)
+// and streams its columns out instead: 144 full-size regions, 1024 columns 12.8 ms,
+// against 17.3 with the update's hints on the same box (profiles/train_drive.md).
+
+// a column is written once and read later by the Gram kernel: streamed past the L2,
+// which the region's A rows are to stay in
+__device__ inline void drive_store(double *p, double v) { __builtin_nontemporal_store(v, p); }
+
+template <typename WT>
+__global__ __launch_bounds__(kUpdThreads, 4) void k_res_drive(
+    const RegionDev *__restrict__ R, const int32_t *__restrict__ row0, const int32_t *__restrict__ a_rp,
+    const uint16_t *__restrict__ a_col, const WT *__restrict__ a_val, const int32_t *__restrict__ w_rp,
+    const uint16_t *__restrict__ w_col, const WT *__restrict__ w_val, Ell ell, const double *__restrict__ x_old,
+    double *__restrict__ x_new, const double *__restrict__ inputs, int64_t stride, const double *__restrict__ model,
+    int64_t model_stride, const int32_t *__restrict__ tgt_idx, double *__restrict__ states,
+    double *__restrict__ targets, int m, int ncs, int nout, double leak, int lds_x, int lds_u) {
+    extern __shared__ __attribute__((aligned(16))) double smem[];
+    const int r = blockIdx.x, tid = threadIdx.x;
+    const RegionDev rg = R[r];
+    const int n = rg.n, ninp = rg.ninp;
+    const CsrRows<WT> csr{a_rp + rg.a_rp, a_col + rg.a_nz, a_val + rg.a_nz, w_rp + rg.w_rp, w_col + rg.w_nz,
+                          w_val + rg.w_nz};
+    double *sx = smem, *su = smem + 2 * (size_t)lds_x;  // [2][lds_x] states, [2][lds_u] inputs
+    const double *u = inputs + rg.fb;
+    RowRegs<WT> cur, nxt;
+    load_row<WT, false>(cur, rg, ell, tid, tid < n);
+    for (int j = tid; j < n; j += kUpdThreads) sx[j] = x_old[rg.x + j];
+    for (int j = tid; j < ninp; j += kUpdThreads) su[j] = u[j];
+    __syncthreads();
+    double *scol = states + (int64_t)m * (row0[r] + (int64_t)r * ncs);
+    double *tcol = targets ? targets + (int64_t)m * r * nout : nullptr;
+    const int32_t *ti = tgt_idx + (size_t)r * nout;
+    const double *lm = model + (size_t)r * ncs;
+    const bool ureg = ninp <= kUpdThreads;  // the next input through one register per thread
+    int b = 0;
+    for (int c = 0; c < m; ++c) {  // (every bound below is block-uniform)
+        const double *xs = sx + (size_t)b * lds_x, *fs = su + (size_t)b * lds_u;
+        double *xn = sx + (size_t)(1 - b) * lds_x, *un = su + (size_t)(1 - b) * lds_u;
+        const bool more = c + 1 < m;
+        const double *unext = u + (size_t)(c + 1) * stride;
+        double uv = 0.0;
+        if (more && ureg && tid < ninp) uv = unext[tid];
+        for (int j = tid; j < ncs; j += kUpdThreads) drive_store(scol + j, lm[j]);
+        if (tcol)
+            for (int j = tid; j < nout; j += kUpdThreads) drive_store(tcol + j, fs[ti[j]]);
+        for (int base = 0; base < n; base += kUpdThreads) {
+            const int i = base + tid, inext = i + kUpdThreads;
+            if (base + kUpdThreads < n)
+                load_row<WT, false>(nxt, rg, ell, inext, inext < n);
+            else if (more)
+                load_row<WT, false>(nxt, rg, ell, tid, tid < n);  // the next column's first pass
+            if (i < n) {
+                const double xv = xs[i];
+                drive_store(scol + ncs + i, (i & 1) ? xv * xv : xv);
+                xn[i] = row_value(cur, rg, ell, csr, xs, fs, i, leak);
+            }
+            cur = nxt;
+        }
+        if (more) {
+            if (ureg) {
+                if (tid < ninp) un[tid] = uv;
+            } else {
+                for (int j = tid; j < ninp; j += kUpdThreads) un[j] = unext[j];
+            }
+        }
+        __syncthreads();  // x_new and u_{c+1} complete; every read of x and u_c done
+        b = 1 - b;
+        scol += ncs + n;
+        if (tcol) tcol += nout;
+        lm += model_stride;
+    }
+    const double *xs = sx + (size_t)b * lds_x;
+    for (int j = tid; j < n; j += kUpdThreads) x_new[rg.x + j] = xs[j];
+}
+
+// column c of every region from the state in global memory: the stepwise form of the
+// drive (SML_RES_PATH_STEPWISE_DRIVE, or a region past k_res_drive's LDS), followed by
+// the update's own launch.  grid (nlocal, row chunks of 256)
+__global__ __launch_bounds__(256) void k_drive_record(const RegionDev *__restrict__ R,
+                                                      const int32_t *__restrict__ row0,
+                                                      const double *__restrict__ x, const double *__restrict__ u,
+                                                      const double *__restrict__ lm,
+                                                      const int32_t *__restrict__ tgt_idx,
+                                                      double *__restrict__ states, double *__restrict__ targets,
+                                                      int c, int m, int ncs, int nout) {
+    const int r = blockIdx.x, j = blockIdx.y * blockDim.x + threadIdx.x;
+    const RegionDev rg = R[r];
+    const int naug = ncs + rg.n;
+    double *scol = states + (int64_t)m * (row0[r] + (int64_t)r * ncs) + (int64_t)c * naug;
+    if (j < ncs) {
+        scol[j] = lm[(size_t)r * ncs + j];
+    } else if (j < naug) {
+        const int i = j - ncs;
+        const double xv = x[rg.x + i];
+        scol[j] = (i & 1) ? xv * xv : xv;
+    }
+    if (targets && blockIdx.y == 0) {
+        double *tcol = targets + ((int64_t)m * r + c) * nout;
+        for (int t = threadIdx.x; t < nout; t += blockDim.x) tcol[t] = u[rg.fb + tgt_idx[(size_t)r * nout + t]];
     }
 }
 
@@ -1204,6 +1355,15 @@ int build_tables(sml_reservoirs *c) {
         (rc = dalloc(&c->d_tisr_grid, tgi.size())) || (rc = dalloc(&c->d_tisr_reg, treg.size())))
         return rc;
     c->tot_tisr = (int)tfb.size();
+    // the training targets' positions in each local region's feedback (the drive's gather)
+    std::vector<int32_t> tidx((size_t)c->nlocal * c->nout, 0);
+    for (int i = 0; i < c->nlocal; ++i) {
+        std::vector<int32_t> t((size_t)(kVars * kZGrid + 2) * c->geom[i].inx * c->geom[i].iny);
+        const int cnt = region_target_index(c->geom[i], t.data());
+        SML_REQUIRE(cnt == c->nout, "region %d: %d training targets, nout %d", i, cnt, c->nout);
+        std::copy(t.begin(), t.begin() + cnt, tidx.begin() + (size_t)i * c->nout);
+    }
+    if ((rc = dalloc(&c->d_tgt_idx, tidx.size())) || (rc = upload(c->d_tgt_idx, tidx))) return rc;
     if ((rc = upload(c->d_tisr_fb, tfb)) || (rc = upload(c->d_tisr_grid, tgi)) || (rc = upload(c->d_tisr_reg, treg)))
         return rc;
     SML_HIP(hipMemcpy(c->d_asm_dst, dst.data(), dst.size() * 4, hipMemcpyHostToDevice));
@@ -1455,7 +1615,8 @@ extern "C" int sml_res_destroy(sml_reservoirs *c) {
     void *ptrs[] = {c->d_rd,    c->d_a_rp,    c->d_w_rp,   c->d_a_col,  c->d_w_col,  c->d_a_val,  c->d_w_val,
                     c->d_wout,  c->d_x[0],    c->d_x[1],   c->d_meanstd, c->d_outl,  c->d_asm_dst,
                     c->d_fb_src, c->d_fb_l,   c->d_fb_reg, c->d_lm_src, c->d_lm_l,   c->d_io,     c->d_part,
-                    c->d_wlm,   c->d_tisr_fb, c->d_tisr_grid, c->d_tisr_reg, c->d_row0, c->d_blk_r0};
+                    c->d_wlm,   c->d_tisr_fb, c->d_tisr_grid, c->d_tisr_reg, c->d_row0, c->d_blk_r0,
+                    c->d_tgt_idx};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
     for (hipEvent_t e : c->ev)
@@ -1777,9 +1938,10 @@ extern "C" int sml_res_ell_layout(sml_reservoirs *c, int i, int *a_width, int *a
 // only where a region's structure does not fit): SML_RES_PATH_CSR -- A and W_in from
 // their CSR copies, no ELL layout (before any region is loaded); SML_RES_PATH_PER_REGION
 // -- k_res_update, a block per (region, part), instead of the balanced update;
-// SML_RES_PATH_UNGROUPED_FINISH -- the v_p finish one thread per output
+// SML_RES_PATH_UNGROUPED_FINISH -- the v_p finish one thread per output;
+// SML_RES_PATH_STEPWISE_DRIVE -- the training drive one update launch per column
 extern "C" int sml_res_set_reference_paths(sml_reservoirs *c, int flags) {
-    SML_REQUIRE(c && (flags & ~7) == 0, "bad argument");
+    SML_REQUIRE(c && (flags & ~15) == 0, "bad argument");
     const bool csr = flags & SML_RES_PATH_CSR;
     if (csr != c->no_ell) {
         for (unsigned char l : c->loaded)
@@ -1795,6 +1957,7 @@ extern "C" int sml_res_set_reference_paths(sml_reservoirs *c, int flags) {
     }
     c->upd_bal = !(flags & SML_RES_PATH_PER_REGION);
     c->finish_ungrouped = flags & SML_RES_PATH_UNGROUPED_FINISH;
+    c->stepwise_drive = flags & SML_RES_PATH_STEPWISE_DRIVE;
     return SML_OK;
 }
 
@@ -2257,6 +2420,65 @@ extern "C" int sml_res_synchronize(sml_reservoirs *c, const double *d_inputs, in
             return rc;
         c->cur = 1 - c->cur;
     }
+    return SML_OK;
+}
+
+namespace {
+// k_res_drive's LDS: two states and two inputs of the largest region
+size_t drive_lds(const sml_reservoirs *c) {
+    return 2 * (size_t)((c->maxn + 1) / 2 * 2 + c->maxninp) * sizeof(double);
+}
+}  // namespace
+
+// the training drive (k_res_drive above): "record, then advance" over one batch of m
+// columns for every local region.  Stream-ordered, no host synchronisation.
+extern "C" int sml_res_train_drive(sml_reservoirs *c, const double *d_inputs, int m, int64_t stride,
+                                   const double *d_model, int64_t model_stride, double *d_states,
+                                   double *d_targets, void *stream) {
+    SML_REQUIRE(c && m >= 0, "bad argument");
+    if (c->nlocal == 0 || m == 0) return SML_OK;
+    SML_REQUIRE(d_inputs && stride >= (int64_t)c->tot_fb, "stride smaller than the packed feedback size");
+    SML_REQUIRE(d_states, "null device buffer");
+    SML_REQUIRE(c->ncs == 0 || (d_model && model_stride >= (int64_t)c->nlocal * c->ncs),
+                "model_stride smaller than nlocal * chunk_speedy (or d_model null)");
+    SML_REQUIRE(!d_targets || !c->generic, "a generic (slab) context has no target geometry: d_targets must be NULL");
+    if (c->begun) return fail(SML_ERR_STATE, "sml_res_train_drive inside a begun step");
+    if (int rc = check_loaded(c)) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    if (c->ncs == 0) {
+        d_model = nullptr;
+        model_stride = 0;
+    }
+    const size_t lds = drive_lds(c);
+    if (c->stepwise_drive || lds > c->max_lds) {
+        const int chunks = (c->ncs + c->maxn + 255) / 256;
+        for (int t = 0; t < m; ++t) {
+            const double *u = d_inputs + (size_t)t * stride;
+            hipLaunchKernelGGL(k_drive_record, dim3(c->nlocal, chunks), dim3(256), 0, st, c->d_rd, c->d_row0,
+                               c->d_x[c->cur], u, d_model + (size_t)t * model_stride, c->d_tgt_idx, d_states,
+                               d_targets, t, m, c->ncs, c->nout);
+            if (int rc = launch_update(c, c->d_x[c->cur], c->d_x[1 - c->cur], u, st)) return rc;
+            c->cur = 1 - c->cur;
+        }
+        SML_HIP(hipGetLastError());
+        return SML_OK;
+    }
+    const int lds_x = (c->maxn + 1) / 2 * 2;
+    const Ell ell = make_ell(c);
+    auto go = [&](auto wt_tag) {
+        using WT = decltype(wt_tag);
+        hipLaunchKernelGGL(k_res_drive<WT>, dim3(c->nlocal), dim3(kUpdThreads), lds, st, c->d_rd, c->d_row0,
+                           c->d_a_rp, c->d_a_col, (const WT *)c->d_a_val, c->d_w_rp, c->d_w_col,
+                           (const WT *)c->d_w_val, ell, c->d_x[c->cur], c->d_x[1 - c->cur], d_inputs, stride, d_model,
+                           model_stride, c->d_tgt_idx, d_states, d_targets, m, c->ncs, c->nout, c->leakage, lds_x,
+                           c->maxninp);
+    };
+    if (c->wdtype == SML_F32)
+        go(float{});
+    else
+        go(double{});
+    SML_HIP(hipGetLastError());
+    c->cur = 1 - c->cur;
     return SML_OK;
 }
 

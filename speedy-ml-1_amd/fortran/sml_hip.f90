@@ -597,6 +597,27 @@ module sml_hip
       integer(c_int), intent(out) :: g(12)
       integer(c_int) :: rc
     end function
+    !> the training targets' 0-based positions in the region's feedback vector
+    !> (tile_full_input_to_target_data2d, res_domain.f90:602-651): 34 resx resy entries
+    function sml_region_target_index(numregions, region, sst, idx, count) &
+        bind(C, name='sml_region_target_index') result(rc)
+      import :: c_int, c_int32_t
+      integer(c_int), value :: numregions, region, sst
+      integer(c_int32_t), intent(out) :: idx(*)
+      integer(c_int), intent(out) :: count
+      integer(c_int) :: rc
+    end function
+    !> the training drive (reservoir_layer_chunking_hybrid, mod_reservoir.f90:1065-1173):
+    !> m columns of augmented states and targets for sml_train_accumulate, then the state
+    !> advanced over the m inputs (device pointers; d_targets may be c_null_ptr)
+    function sml_res_train_drive(ctx, d_inputs, m, stride, d_model, model_stride, d_states, d_targets, stream) &
+        bind(C, name='sml_res_train_drive') result(rc)
+      import :: c_ptr, c_int, c_int64_t
+      type(c_ptr), value :: ctx, d_inputs, d_model, d_states, d_targets, stream
+      integer(c_int), value :: m
+      integer(c_int64_t), value :: stride, model_stride
+      integer(c_int) :: rc
+    end function
     !> processor_decomposition (res_domain.f90:31-62), 0-based regions
     function sml_processor_decomposition(numregions, numprocs, irank, regions, count) &
         bind(C, name='sml_processor_decomposition') result(rc)

@@ -63,12 +63,13 @@ EXPORTED = (
     "sml_dyn_set_climatology", "sml_dyn_fordate", "sml_dyn_fordate_ex", "sml_dyn_fordate_count",
     "sml_hybrid_set_calendar", "sml_hybrid_window_date", "sml_hybrid_set_hop_timeout",
     "sml_dyn_set_check_timeout", "sml_dyn_check_stream", "sml_dyn_set_fused", "sml_res_set_reference_paths",
-    "sml_train_set_panel",
+    "sml_train_set_panel", "sml_res_train_drive", "sml_region_target_index",
 )
 
 SML_HOP_AUTO, SML_HOP_WAIT_VALUE, SML_HOP_EVENTS, SML_HOP_KERNEL = 0, 1, 2, 3
 SML_CHAIN_AUTO, SML_CHAIN_TWO_STREAMS, SML_CHAIN_SPEEDY = 0, 1, 2
 SML_RES_PATH_CSR, SML_RES_PATH_PER_REGION, SML_RES_PATH_UNGROUPED_FINISH = 1, 2, 4
+SML_RES_PATH_STEPWISE_DRIVE = 8
 
 
 class SmlError(RuntimeError):
@@ -265,6 +266,8 @@ def _declare(L: ctypes.CDLL) -> None:
         "sml_hybrid_set_calendar": [vp, i, ctypes.c_int64, i],
         "sml_hybrid_window_date": [vp, ip],
         "sml_hybrid_set_hop_timeout": [vp, ctypes.c_int64],
+        "sml_res_train_drive": [vp, vp, i, ctypes.c_int64, vp, ctypes.c_int64, vp, vp, vp],
+        "sml_region_target_index": [i, i, i, vp, ip],
     }
     for name, args in sig.items():
         if os.environ.get("SML_LIB") and not hasattr(L, name):

@@ -152,12 +152,51 @@ class Reservoirs:
         check(lib().sml_res_ell_layout(self._h, int(i), *[ctypes.byref(x) for x in v]))
         return dict(a_width=v[0].value, a_overflow=bool(v[1].value), win_q=v[2].value, win_ell=bool(v[3].value))
 
-    def set_reference_paths(self, csr: bool = False, per_region: bool = False, ungrouped_finish: bool = False):
+    def set_reference_paths(self, csr: bool = False, per_region: bool = False, ungrouped_finish: bool = False,
+                            stepwise_drive: bool = False):
         """Force the fallback paths for every region (sml_res_set_reference_paths): A /
         W_in from their CSR copies (before any region is loaded), the per-region state
-        update, the v_p finish one thread per output -- bitwise the defaults."""
-        flags = (1 if csr else 0) | (2 if per_region else 0) | (4 if ungrouped_finish else 0)
+        update, the v_p finish one thread per output, the training drive one update
+        launch per column -- bitwise the defaults."""
+        flags = ((1 if csr else 0) | (2 if per_region else 0) | (4 if ungrouped_finish else 0)
+                 | (8 if stepwise_drive else 0))
         check(lib().sml_res_set_reference_paths(self._h, flags))
+
+    def target_index(self, i: int) -> np.ndarray:
+        """0-based positions of local region i's training targets inside its feedback
+        vector (sml_region_target_index)."""
+        idx = np.zeros(34 * 96 * 48 // self.numregions, dtype=np.int32)
+        cnt = ctypes.c_int()
+        check(lib().sml_region_target_index(self.numregions, int(self.region_ids[i]), int(self.sst[i]), ptr(idx),
+                                            ctypes.byref(cnt)))
+        return idx[:cnt.value]
+
+    def train_drive(self, d_inputs, m: int, d_model, d_states, d_targets=None, stride: int | None = None,
+                    model_stride: int | None = None, stream=None):
+        """The training drive (sml_res_train_drive; reservoir_layer_chunking_hybrid,
+        mod_reservoir.f90:1065-1173): for each of the m input blocks of d_inputs, column c
+        of every region's block of d_states = [model block c; the current state with its
+        odd nodes squared], column c of d_targets = the region's targets of block c, then
+        the state advances on block c.  d_states / d_targets are packed as
+        Trainer.accumulate reads them.  d_model: m blocks of [nlocal][ncs] (None when
+        chunk_speedy == 0).  The series is taken as given: input noise
+        (gaussian_noise_1d_function) is the caller's."""
+        stride = int(self.fb_offsets[-1]) if stride is None else int(stride)
+        model_stride = self.nlocal * self.ncs if model_stride is None else int(model_stride)
+        if m < 0:
+            raise ValueError("m must be >= 0")
+        if m > 0:
+            if d_inputs.numel() < (m - 1) * stride + int(self.fb_offsets[-1]):
+                raise ValueError("d_inputs holds fewer than m blocks of `stride` doubles")
+            if self.ncs and (d_model is None or d_model.numel() < (m - 1) * model_stride + self.nlocal * self.ncs):
+                raise ValueError("d_model holds fewer than m blocks of `model_stride` doubles")
+            if d_states.numel() < m * (int(self.n.sum()) + self.nlocal * self.ncs):
+                raise ValueError("d_states is smaller than m * sum(ncs + n)")
+            if d_targets is not None and d_targets.numel() < m * self.nlocal * self.nout:
+                raise ValueError("d_targets is smaller than m * nlocal * nout")
+        check(lib().sml_res_train_drive(self._h, ptr(d_inputs), int(m), stride,
+                                        ptr(d_model if self.ncs else None), model_stride, ptr(d_states),
+                                        ptr(d_targets), stream_ptr(stream)))
 
     def set_begin_mode(self, mode: int):
         """predict_begin's form: 0 update grid + readout grid, 1 / 2 one fused launch

@@ -85,3 +85,56 @@ class Trainer:
         B = np.zeros((self.nout, self.npad))
         check(lib().sml_train_get_gram(self._h, i, ptr(G), ptr(B)))
         return G, B
+
+
+def train_wout(res, d_inputs, d_model, discard: int, batch: int, nbatches: int, ncs: int = 132,
+               beta_res: float = 0.001, beta_model: float = 1.0, using_prior: bool = True, prior_val: float = 0.0,
+               dtype=np.float32, stream=None):
+    """Train W_out of every local region of `res` (a Reservoirs with A and W_in loaded)
+    from a training series on the device: the reference's train_reservoir tail,
+    reservoir_layer_chunking_hybrid + chunking_matmul + fit_chunk_hybrid
+    (src/mod_reservoir.f90:1065-1173, :1643-1699, :1233-1332).
+
+    d_inputs: (discard + batch * nbatches, total feedback) packed input blocks;
+    d_model:  the same number of (nlocal, ncs) model blocks (None when ncs == 0).
+    The states start at zero and run `discard` updates (Reservoirs.synchronize); batch b
+    is then one Reservoirs.train_drive over blocks discard + b * batch .. + batch - 1
+    followed by Trainer.accumulate; Trainer.solve closes.  The series is used as given:
+    the reference's input noise (gaussian_noise_1d_function) is the caller's to add.
+
+    Returns (wouts, info): per region W_out as a float32 (ncs + n, nout) array -- C order
+    of the file's wout(nout, ncs + n), NF90_REAL, ready for write_region_netcdf /
+    Reservoirs.load_region -- and the per-region potrf info.  dtype=np.float64 keeps
+    the solve's own precision (the float32 arrays are its rounding)."""
+    import torch
+
+    if ncs != res.ncs:
+        raise ValueError(f"ncs {ncs} differs from the context's chunk_speedy {res.ncs}")
+    nblocks = discard + batch * nbatches
+    tot = int(res.fb_offsets[-1])
+    d_inputs = d_inputs.reshape(-1)
+    if d_inputs.numel() < nblocks * tot:
+        raise ValueError("d_inputs holds fewer than discard + batch * nbatches input blocks")
+    nmod = res.nlocal * ncs
+    if ncs:
+        d_model = d_model.reshape(-1)
+        if d_model.numel() < nblocks * nmod:
+            raise ValueError("d_model holds fewer than discard + batch * nbatches model blocks")
+    naug = [ncs + int(n) for n in res.n]
+    for i, n in enumerate(res.n):
+        res.set_state(i, np.zeros(int(n)))
+    res.synchronize(d_inputs, discard, stream=stream)
+    tr = Trainer(naug, res.nout)
+    tr.reset(stream=stream)
+    states = torch.empty(sum(naug) * batch, dtype=torch.float64, device=d_inputs.device)
+    targets = torch.empty(len(naug) * batch * res.nout, dtype=torch.float64, device=d_inputs.device)
+    for b in range(nbatches):
+        t0 = discard + b * batch
+        res.train_drive(d_inputs[t0 * tot:], batch, d_model[t0 * nmod:] if ncs else None, states, targets,
+                        stream=stream)
+        tr.accumulate(states, targets, batch, stream=stream)
+    packed, info = tr.solve(ncs=ncs, beta_res=beta_res, beta_model=beta_model, using_prior=using_prior,
+                            prior_val=prior_val, stream=stream)
+    wouts = [v.cpu().numpy().astype(dtype) for v in tr.wout_views(packed)]
+    tr.close()
+    return wouts, info
