@@ -1299,8 +1299,9 @@ __global__ __launch_bounds__(kRowThreads) void k_st_rows(const double *__restric
 // phypar's 41 level-1 fields) on lane pairs; then waves 0-1 run the grid-point dynamics
 // and products (one column per thread, F -> B), waves 2-3 phypar's moist part and
 // vdifsc (one column per lane, its results handed over in B's spare columns), waves 4-6
-// the longwave / surface chain -- on a shortwave step after its own moist part and the
-// shortwave -- on two lanes per column (sml_physics_pair.hpp), which then sum the
+// the longwave / surface chain -- on a shortwave step after the shortwave, whose cloud-free
+// part they run while the moist side works, the rest after its hand-over -- on two lanes
+// per column (sml_physics_pair.hpp), which then sum the
 // tendencies into F (phys_column's sums, four levels per lane); then specx of the 73
 // forward transforms (F + P where grtend adds it, x cosgr(j) for vdspec's inputs) on
 // lane pairs straight into the m-major coefficients.  Every expression and sum order is
@@ -1327,7 +1328,8 @@ __global__ __launch_bounds__(kGpThreads) void k_st_gridspec_p(
     __shared__ GpTab gpt;
     __shared__ double fsr[4 * kIX];  // radlw(1)'s surface row per (column, band), sfc_fband
     constexpr int kMh = 3 + kKX;
-    __shared__ double mhs[kIX * kMh];  // a shortwave step's moist-part hand-over (precnv, precls, itop, rh)
+    // a shortwave step's moist-part hand-over (precnv, precls, itop, rh); then the pair lanes' tt_rsw
+    __shared__ double mhs[kIX * kMh];
     constexpr int n1 = kNInv1P;
     constexpr int nphys = (n1 - kPT1) + (kNInvP - (n1 + 2 * kKX + 2));  // 25 + 16 = 41
     const int j = blockIdx.x, tid = threadIdx.x;
@@ -1422,6 +1424,14 @@ __global__ __launch_bounds__(kGpThreads) void k_st_gridspec_p(
             for (int k = 0; k < kKX; ++k) m[3 + k] = mth.rh[k];
         }
     }
+    // a shortwave step's pair lanes, while the moist side works: what needs neither its
+    // hand-over nor the cloud (they reached the barrier idle: 2.2 us of the step, 3.0 on
+    // the tropical rows)
+    PairSw psw;
+    if (isp && lradsw) {
+        phys_pair_sw_pre<kPT1, kPQ1, kPPhi1, kPPs1>(ph_, ppt, A + pi * kRowLd, bc, PTl, psw);
+        SML_PST_T(21, 256);
+    }
     if (lradsw) __syncthreads();
     if (ism) {
         double ttv[kKX], qtv[kKX];
@@ -1438,13 +1448,12 @@ __global__ __launch_bounds__(kGpThreads) void k_st_gridspec_p(
         Bh[23] = qtv[kKX - 1];
         SML_PST_T(13, 128);
     } else if (isp) {  // the longwave / surface chain (and the shortwave) of column pi, two lanes
-        PairPre pre;
-        pair_pre_load(pre);  // (before gridx instead: the gridx lanes' registers spilled, gridx 3.3 -> 3.9 us)
+        // (pair_pre_load before gridx instead: the gridx lanes' registers spilled, gridx 3.3 -> 3.9 us)
         const double *Ai = A + pi * kRowLd;
         const double u7 = Ai[n1 + 2 * kKX + 2 + kKX - 1] * cj, v7 = Ai[n1 + 3 * kKX + 2 + kKX - 1] * cj;
         const double fs2[2] = {fsr[4 * pi + 2 * ph_], fsr[4 * pi + 2 * ph_ + 1]};
-        phys_pair<kPT1, kPQ1, kPPhi1, kPPs1>(ph_, ppt, j, Ai, u7, v7, pre, bc, rad, PTl, &PT->fband[0][0], fs2,
-                                             mhs + pi * kMh, lradsw != 0, po);
+        phys_pair<kPT1, kPQ1, kPPhi1, kPPs1>(ph_, ppt, j, Ai, u7, v7, pair_pre_load, bc, rad, PTl,
+                                             &PT->fband[0][0], fs2, mhs + pi * kMh, lradsw != 0, psw, po);
         SML_PST_T(18, 256);
         SML_PST_T(19, 384);
     }
@@ -1452,12 +1461,13 @@ __global__ __launch_bounds__(kGpThreads) void k_st_gridspec_p(
     SML_PST_T(20, 256);
     if (isp) {  // phys_column's sums (phy_phypar.f90:174-196), the pair lane's four levels
         const double *Bh = B + pi * kRowLd + kNFwd;
+        const double *Mh = mhs + pi * kMh;  // the lane's levels of the shortwave heating (phys_pair)
         double *Bi = B + pi * kRowLd;
         const double rps = po.rps;
 #pragma unroll
         for (int s = 0; s < 4; ++s) {
             const int k = 4 * ph_ + s;
-            const double ttk = (k == 0 ? 0.0 : Bh[k > 0 ? k - 1 : 0]) + po.rsw[s] + po.rlw[s];
+            const double ttk = (k == 0 ? 0.0 : Bh[k > 0 ? k - 1 : 0]) + Mh[4 * ph_ + s] + po.rlw[s];
             double ttv = Bh[7 + k], utv = 0., vtv = 0.;
             double qtk;
             if (k == kKX - 1) {
@@ -1966,16 +1976,21 @@ __global__ void k_set_xa(uint64_t *xa, uint64_t v0, uint64_t v1, uint64_t v2, ui
 // one lane polls *go (stored by the window's first row kernel) and acquires at agent
 // scope; the check's kernels follow on the stream.  Never spins forever: on a timeout it
 // marks *late with late_value (the exit's target for this check, so sml_dyn_last_safe
-// fails this window) and the check reads whatever d_chk holds
+// fails this window) and the check reads whatever d_chk holds.  The give-up time is
+// tested before each poll, so a zero give-up time gives up at once whichever of this
+// kernel and the window's first row kernel -- dispatched side by side -- starts first
+// (polled first, it gave up only while the row kernel was the slower one to start, which
+// a row kernel without scratch no longer is)
 __global__ void k_check_go(const uint64_t *go, uint64_t want, unsigned *late, unsigned late_value, long long timeout) {
     if (threadIdx.x != 0) return;
     const long long t0 = wall_clock64();
-    while (__hip_atomic_load(go, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < want) {
-        __builtin_amdgcn_s_sleep(2);
-        if (wall_clock64() - t0 > timeout) {
+    for (;;) {
+        if (wall_clock64() - t0 >= timeout) {
             __hip_atomic_store(late, late_value, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
             break;
         }
+        if (__hip_atomic_load(go, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= want) break;
+        __builtin_amdgcn_s_sleep(2);
     }
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
 }

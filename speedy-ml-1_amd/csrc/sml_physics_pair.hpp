@@ -12,6 +12,15 @@
 // cloud and radsw's flux chains; suflux) run on both lanes alike.  The partners trade
 // values by DPP (one row permutation per double, no LDS), so every level's divergence
 // adds the four bands' fluxes in radlw's order: bitwise the one-lane form.
+//
+// A shortwave step in two stages.  The moist side hands its results (precnv, precls, itop,
+// rh) over at a block barrier, and the pair waves have nothing else to do before it: so
+// everything of the shortwave path that reads neither the hand-over nor the cloud runs
+// before that barrier (phys_pair_sw_pre: the A row, psg, the boundary loads, clstr's
+// stability factor, t2, the transmissivities of levels 1, 2 and 8, radlw's blackbody
+// terms -- 10 of the lane's 24 exp evaluations and psg's), and phys_pair does the rest
+// after it.  Whole statements moved, none split: every exp argument and every contracted
+// expression is the same double as in the one-stage form.
 #pragma once
 #include "sml_physics.hpp"
 
@@ -24,9 +33,10 @@ struct PairPre {
     double strat0, strat1, ssrd, ttrsw[4];
 };
 
-// lane h's share of phys_column's results: its four levels, the surface fluxes
+// lane h's share of phys_column's results: its four levels (the shortwave heating: LDS,
+// phys_pair's mh), the surface fluxes
 struct PairOut {
-    double rsw[4], rlw[4];
+    double rlw[4];
     double ust, vst, shf, evp, rps;
 };
 
@@ -40,6 +50,17 @@ __device__ __forceinline__ double sfc_fband(const double *__restrict__ bc, const
     const double tsfc = tsea + fmask * (stl - tsea);
     return phys::fband_row(fbt, tsfc)[jb];
 }
+
+// a shortwave step's values of pair lane h that wait for neither the moist side nor the
+// cloud (phys_pair_sw_pre -> phys_pair across the hand-over barrier)
+struct PairSw {
+    double ta[kKX], qc[kKX], ph7;  // the A row: t, clipped q, the bottom level's phi
+    double psg, rps, fst, psaz;    // exp(ps), its inverse, clstr's stability factor, psg x zenit
+    double fmask, fsol, ozupp, ozone, albsfc, stratz;  // boundary fields of the shortwave path
+    double o2[4];                  // radsw's t2 of the lane's levels
+    double tqe[2][3];              // bands 2h, 2h + 1 at levels 1, 2 and 8
+    double st4a1[kKX], st4a2[kKX];  // radlw(-1)'s blackbody terms
+};
 
 namespace pairx {
 
@@ -56,18 +77,137 @@ __device__ __forceinline__ double own(const double (&a)[kKX], int h, int j) { re
 // level 4 (1 - h) + j (the partner's levels)
 __device__ __forceinline__ double oth(const double (&a)[kKX], int h, int j) { return h ? a[j] : a[4 + j]; }
 
+// radlw(-1)'s blackbody terms (phy_radiat.f90:330-413), which need ta alone
+__device__ __forceinline__ void blackbody(const double (&ta)[kKX], const PhysTables *P, double (&st4a1)[kKX],
+                                          double (&st4a2)[kKX]) {
+    using namespace phys;
+    constexpr int NL = kKX, nl1 = kKX - 1;
+#pragma unroll
+    for (int k = 1; k <= nl1; ++k) st4a1[k - 1] = ta[k - 1] + P->wvi[k - 1][1] * (ta[k] - ta[k - 1]);
+    st4a2[0] = 0.75 * ta[0] + 0.25 * st4a1[0];
+    st4a2[1] = 0.50 * ta[1] + 0.25 * (st4a1[0] + st4a1[1]);
+    {
+        const double anis = 1.0, anish = 0.5 * anis;
+#pragma unroll
+        for (int k = 3; k <= nl1; ++k) st4a2[k - 1] = anish * fmax(st4a1[k - 1] - st4a1[k - 2], 0.);
+        st4a2[NL - 1] = anis * fmax(ta[NL - 1] - st4a1[nl1 - 1], 0.);
+    }
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+        const double x = st4a2[k];
+        st4a1[k] = sbc * ((x * x) * (x * x));
+        st4a2[k] = 0.;
+    }
+#pragma unroll
+    for (int k = 3; k <= NL; ++k) {
+        const double t = ta[k - 1];
+        const double st3a = sbc * (t * t * t);
+        st4a1[k - 1] = st3a * t;
+        st4a2[k - 1] = 4. * st3a * st4a2[k - 1];
+    }
+}
+
 }  // namespace pairx
+
+// The first stage of a shortwave step on pair lane h (column pt, its row Ai in A): what
+// phys_pair's shortwave path needs that depends on neither the moist side's hand-over
+// nor the cloud, run while the moist side works.
+template <int kOT, int kOQ, int kOPhi, int kOPs>
+__device__ __forceinline__ void phys_pair_sw_pre(int h, int pt, const double *Ai, const double *__restrict__ bc,
+                                                 const PhysTables *P, PairSw &w) {
+    using namespace phys;
+    using pairx::own;
+    constexpr int NL = kKX;
+    auto BC = [&](int f) { return bc[(size_t)f * kNGP + pt]; };
+    // the boundary loads first: memory round trips that the arithmetic below covers
+    w.fmask = BC(kBcFmask1);
+    const double zenit = BC(kBcZenit);
+    w.fsol = BC(kBcFsol);
+    w.ozupp = BC(kBcOzupp);
+    w.ozone = BC(kBcOzone);
+    w.albsfc = BC(kBcAlbsfc);
+    w.stratz = BC(kBcStratz);
+    double qa[NL], ph[NL];
+#pragma unroll
+    for (int k = 0; k < NL; ++k) {
+        w.ta[k] = Ai[kOT + k];
+        qa[k] = Ai[kOQ + k];
+        ph[k] = Ai[kOPhi + k];
+    }
+    const double ps1 = Ai[kOPs];
+    w.ph7 = ph[NL - 1];
+    const double psg = exp(ps1);
+    w.psg = psg;
+    w.rps = 1. / psg;
+#pragma unroll
+    for (int k = 0; k < NL; ++k) w.qc[k] = fmax(qa[k], 0.);
+    double se[NL];
+#pragma unroll
+    for (int k = 0; k < NL; ++k) se[k] = cp * w.ta[k] + ph[k];
+    const double gse = (se[NL - 2] - se[NL - 1]) / (ph[NL - 2] - ph[NL - 1]);
+    {
+        const double rgse = 1. / (gse_s1 - gse_s0);
+        const double fst = fmax(0., fmin(1., rgse * (gse - gse_s0)));
+        w.fst = fst;
+    }
+    // radsw's t2 of the lane's levels (phy_radiat.f90:190-214; the top level has none)
+    const double psaz = psg * zenit;
+    w.psaz = psaz;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int L = 4 * h + j, k = L + 1;
+        const double qk = own(w.qc, h, j);
+        const double e2 = exp(-(psaz * P->dsig[k - 1]) * abswv2 * qk);
+        w.o2[j] = L >= 1 ? e2 : 0.0;
+    }
+    // the longwave transmissivities outside the cloud's levels: k = 1, 2 and 8 of bands
+    // 2h, 2h + 1 (phy_radiat.f90:262-300; bands 2 and 3 are 1 at the top level)
+#pragma unroll
+    for (int b = 0; b < 2; ++b) {
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+            const int k = i < 2 ? i + 1 : NL;
+            const double deltap = psg * P->dsig[k - 1];
+            const double qk = w.qc[k - 1];
+            double e;
+            if (k == 1) {  // bands 0 and 1 (lane 0)
+                const double a0 = -deltap * ablwin;
+                const double a1 = -deltap * ablco2;
+                e = exp(b == 0 ? a0 : a1);
+                e = h ? 1. : e;
+            } else if (b == 0) {  // band 0 (h = 0) or 2 (h = 1)
+                const double a0 = -deltap * ablwin;
+                const double a2 = -deltap * ablwv1 * qk;
+                e = exp(h ? a2 : a0);
+            } else {  // band 1 (h = 0) or 3 (h = 1)
+                const double a1 = -deltap * ablco2;
+                const double a3 = -deltap * ablwv2 * qk;
+                e = exp(h ? a3 : a1);
+            }
+            w.tqe[b][i] = e;
+        }
+    }
+    pairx::blackbody(w.ta, P, w.st4a1, w.st4a2);
+}
 
 // The longwave / surface chain of column pt on pair lane h (and the shortwave before it
 // on a lradsw step).  Ai: the column's row in A (t, q, phi at kOT / kOQ / kOPhi + k,
 // log ps at kOPs); u7 / v7: the bottom level's wind (x cosgr); fsr: fband(nint(tsfc),
 // 2h + b) for b = 0, 1; P: PhysTables (LDS copy); fbt: fband (global); mh: on a
-// shortwave step the moist side's precnv, precls, itop and rh of the column (LDS).
-template <int kOT, int kOQ, int kOPhi, int kOPs>
+// shortwave step the moist side's precnv, precls, itop and rh of the column (LDS); sw: on
+// a shortwave step the first stage's values (phys_pair_sw_pre, before the hand-over);
+// pre_load(PairPre &): loads a longwave-only step's radiation state.  The lane's four
+// levels of the shortwave heating tt_rsw are not needed before the sums: they wait in LDS,
+// mh[4h + j] (the hand-over's slots, read by then), not in registers held through radlw
+// and suflux (which went to scratch, on a longwave-only step between its loads).  The two kinds of
+// step share no branch but the one below: the first stage's values (sw) and the radiation
+// state (PairPre) are never live together (as two branches in a row they were, and the
+// longwave-only step spilled loaded values between its loads, +0.2 us).
+template <int kOT, int kOQ, int kOPhi, int kOPs, class PreLoad>
 __device__ __forceinline__ void phys_pair(int h, int pt, int jlat, const double *Ai, double u7, double v7,
-                                          const PairPre &pre, const double *__restrict__ bc, double *__restrict__ rad,
+                                          PreLoad &&pre_load, const double *__restrict__ bc, double *__restrict__ rad,
                                           const PhysTables *P, const double *__restrict__ fbt, const double (&fsr)[2],
-                                          const double *mh, bool lradsw, PairOut &o) {
+                                          double *mh, bool lradsw, const PairSw &sw, PairOut &o) {
     using namespace phys;
     using pairx::oth;
     using pairx::own;
@@ -75,16 +215,10 @@ __device__ __forceinline__ void phys_pair(int h, int pt, int jlat, const double 
     constexpr int NL = kKX, nl1 = kKX - 1;  // nl1: 1-based index of the level above the bottom
     auto BC = [&](int f) { return bc[(size_t)f * kNGP + pt]; };
 
-    double ta[NL], qa[NL], ph[NL];
-#pragma unroll
-    for (int k = 0; k < NL; ++k) {
-        ta[k] = Ai[kOT + k];
-        qa[k] = Ai[kOQ + k];
-        ph[k] = Ai[kOPhi + k];
-    }
-    const double ps1 = Ai[kOPs];
-    // bands 2h, 2h + 1's fband rows (radlw, both passes): issued as soon as ta is known on a
-    // longwave-only step, after the shortwave on a shortwave step (registers)
+    // the A row (on a shortwave step the first stage read it); bands 2h, 2h + 1's fband
+    // rows (radlw, both passes): issued as soon as ta is known on a longwave-only step,
+    // after the shortwave on a shortwave step (registers)
+    double ta[NL], ph7;
     double fbq[2][NL];
     auto load_fbq = [&]() {
 #pragma unroll
@@ -92,28 +226,31 @@ __device__ __forceinline__ void phys_pair(int h, int pt, int jlat, const double 
 #pragma unroll
             for (int k = 0; k < NL; ++k) fbq[b][k] = fband_row(fbt, ta[k])[2 * h + b];
     };
-    if (!lradsw) load_fbq();
 
     double psg, rps, qc[NL];
-    double tq[2][NL], strat0, strat1, ssrd, rsw[4];
+    double tq[2][NL], strat0, strat1, ssrd;
+    double st4a1[NL], st4a2[NL];  // radlw(-1)'s blackbody terms
     if (lradsw) {
         // the moist part's results from the moist side (mh: precnv, precls, itop, rh(1..8),
         // phys_moist / phys_thermo's values, handed over at the block barrier of a
-        // shortwave step), then cloud and radsw (phys_sw) level- and band-split
-        psg = exp(ps1);
-        rps = 1. / psg;
-#pragma unroll
-        for (int k = 0; k < NL; ++k) qc[k] = fmax(qa[k], 0.);
-        const double precnv = mh[0], precls = mh[1];
-        const int itop = (int)mh[2];
-        double rh[NL], se[NL];
+        // shortwave step), then cloud and radsw (phys_sw) level- and band-split; what
+        // needs neither comes from the first stage
+        psg = sw.psg;
+        rps = sw.rps;
+        ph7 = sw.ph7;
 #pragma unroll
         for (int k = 0; k < NL; ++k) {
-            rh[k] = mh[3 + k];
-            se[k] = cp * ta[k] + ph[k];
+            ta[k] = sw.ta[k];
+            qc[k] = sw.qc[k];
+            st4a1[k] = sw.st4a1[k];
+            st4a2[k] = sw.st4a2[k];
         }
+        const double precnv = mh[0], precls = mh[1];
+        const int itop = (int)mh[2];
+        double rh[NL];
+#pragma unroll
+        for (int k = 0; k < NL; ++k) rh[k] = mh[3 + k];
         const double *qa_ = qc;
-        const double gse = (se[NL - 2] - se[NL - 1]) / (ph[NL - 2] - ph[NL - 1]);
         constexpr int nlp = NL + 1;
         const double rrcl = 1. / (rhcl2 - rhcl1);
         double cloudc, clstr;
@@ -139,15 +276,16 @@ __device__ __forceinline__ void phys_pair(int h, int pt, int jlat, const double 
         icltop = (itop < icltop) ? itop : icltop;
         const double qcloud = qa_[nl1 - 1];
         {
-            const double clfact = 1.2, rgse = 1. / (gse_s1 - gse_s0);
-            const double fst = fmax(0., fmin(1., rgse * (gse - gse_s0)));
+            const double clfact = 1.2;
+            const double fst = sw.fst;
             clstr = fst * fmax(clsmax - clfact * cloudc, 0.);
             const double clstrl = fmax(clstr, clsminl) * rh[NL - 1];
-            clstr = clstr + BC(kBcFmask1) * (clstrl - clstr);
+            clstr = clstr + sw.fmask * (clstrl - clstr);
         }
-        // radsw's t1, t2 of the lane's levels (phy_radiat.f90:190-214), then the column's
+        // radsw's t1 of the lane's levels (phy_radiat.f90:190-214; t2: the first stage), then
+        // the column's
         const double fband2 = 0.05, fband1 = 1. - fband2;
-        const double psaz = psg * BC(kBcZenit);
+        const double psaz = sw.psaz;
         const double acloud = cloudc * fmin(abscl1 * qcloud, abscl2);
         double t1[NL], t2[NL], t3[NL], dfabs[NL];
         {
@@ -162,8 +300,7 @@ __device__ __forceinline__ void phys_pair(int h, int pt, int jlat, const double 
                 const double ax = -deltap * (abs1 + abswv1 * qk + acloud);
                 const double ay = -deltap * (abs1 + abswv1 * qk);
                 o1[j] = exp(L == 0 ? a0 : (L < NL - 1 && k >= icltop) ? ax : ay);
-                const double e2 = exp(-(psaz * P->dsig[k - 1]) * abswv2 * qk);
-                o2[j] = L >= 1 ? e2 : 0.0;
+                o2[j] = sw.o2[j];
             }
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
@@ -177,13 +314,13 @@ __device__ __forceinline__ void phys_pair(int h, int pt, int jlat, const double 
 #pragma unroll
         for (int k = 0; k < NL; ++k) t3[k] = (k + 1 == icltop) ? albcl * cloudc : 0.0;  // icltop <= nlev only
         t3[NL - 1] = albcls * clstr;
-        const double fsol = BC(kBcFsol);
+        const double fsol = sw.fsol;
         double f1 = fsol * fband1, f2 = fsol * fband2;
         dfabs[0] = f1;
-        f1 = t1[0] * (f1 - BC(kBcOzupp) * psg);
+        f1 = t1[0] * (f1 - sw.ozupp * psg);
         dfabs[0] = dfabs[0] - f1;
         dfabs[1] = f1;
-        f1 = t1[1] * (f1 - BC(kBcOzone) * psg);
+        f1 = t1[1] * (f1 - sw.ozone * psg);
         dfabs[1] = dfabs[1] - f1;
 #pragma unroll
         for (int k = 3; k <= NL; ++k) {
@@ -200,7 +337,7 @@ __device__ __forceinline__ void phys_pair(int h, int pt, int jlat, const double 
             dfabs[k - 1] = dfabs[k - 1] - f2;
         }
         const double fsfcd = f1 + f2;
-        f1 = f1 * BC(kBcAlbsfc);
+        f1 = f1 * sw.albsfc;
 #pragma unroll
         for (int k = NL; k >= 1; --k) {
             dfabs[k - 1] = dfabs[k - 1] + f1;
@@ -209,33 +346,36 @@ __device__ __forceinline__ void phys_pair(int h, int pt, int jlat, const double 
             f1 = f1 + t3[k - 1];
         }
         ssrd = fsfcd;
-        // longwave transmissivities of bands 2h, 2h + 1 (phy_radiat.f90:262-300)
+        // longwave transmissivities of bands 2h, 2h + 1 (phy_radiat.f90:262-300): the levels
+        // the cloud reaches, 3 .. nl1 (1, 2 and 8: the first stage)
         const double acl = cloudc * ablcl2;
 #pragma unroll
         for (int b = 0; b < 2; ++b) {
-            const int jb = 2 * h + b;
 #pragma unroll
-            for (int k = 1; k <= NL; ++k) {
+            for (int k = 3; k <= nl1; ++k) {
                 const double deltap = psg * P->dsig[k - 1];
                 const double qk = qc[k - 1];
-                const bool mid = k >= 3 && k <= nl1;
                 double e;
                 if (b == 0) {  // band 0 (h = 0) or 2 (h = 1)
                     const double acloud1 = (k < icltop) ? acl : ablcl1 * cloudc;
-                    const double a0 = mid ? -deltap * (ablwin + acloud1) : -deltap * ablwin;
-                    const double a2 = mid ? -deltap * fmax(ablwv1 * qk, acl) : -deltap * ablwv1 * qk;
+                    const double a0 = -deltap * (ablwin + acloud1);
+                    const double a2 = -deltap * fmax(ablwv1 * qk, acl);
                     e = exp(h ? a2 : a0);
                 } else {  // band 1 (h = 0) or 3 (h = 1)
                     const double a1 = -deltap * ablco2;
-                    const double a3 = mid ? -deltap * fmax(ablwv2 * qk, acl) : -deltap * ablwv2 * qk;
+                    const double a3 = -deltap * fmax(ablwv2 * qk, acl);
                     e = exp(h ? a3 : a1);
                 }
-                tq[b][k - 1] = (k == 1 && jb >= 2) ? 1. : e;
+                tq[b][k - 1] = e;
             }
+            tq[b][0] = sw.tqe[b][0];
+            tq[b][1] = sw.tqe[b][1];
+            tq[b][NL - 1] = sw.tqe[b][2];
         }
         const double eps1 = epslw / (P->dsig[0] + P->dsig[1]);
-        strat0 = BC(kBcStratz) * psg;
+        strat0 = sw.stratz * psg;
         strat1 = eps1 * psg;
+        double rsw[4];
 #pragma unroll
         for (int j = 0; j < 4; ++j) rsw[j] = own(dfabs, h, j) * rps * P->grdscp[4 * h + j];
         // the column's state for the steps until the next shortwave step
@@ -249,8 +389,24 @@ __device__ __forceinline__ void phys_pair(int h, int pt, int jlat, const double 
             rad[kRadSsrd + pt] = fsfcd;
         }
 #pragma unroll
-        for (int j = 0; j < 4; ++j) rad[kRadTtRsw + (size_t)(4 * h + j) * kNGP + pt] = rsw[j];
-    } else {  // phys_thermo's psg, rps and clipped q; rad's state
+        for (int j = 0; j < 4; ++j) {
+            rad[kRadTtRsw + (size_t)(4 * h + j) * kNGP + pt] = rsw[j];
+            mh[4 * h + j] = rsw[j];
+        }
+        SML_PST_T(15, 256);
+        load_fbq();
+    } else {  // rad's state; the A row; phys_thermo's psg, rps and clipped q
+        PairPre pre;
+        pre_load(pre);
+        double qa[NL];
+#pragma unroll
+        for (int k = 0; k < NL; ++k) {
+            ta[k] = Ai[kOT + k];
+            qa[k] = Ai[kOQ + k];
+        }
+        ph7 = Ai[kOPhi + NL - 1];
+        const double ps1 = Ai[kOPs];
+        load_fbq();
         psg = exp(ps1);
         rps = 1. / psg;
 #pragma unroll
@@ -263,37 +419,13 @@ __device__ __forceinline__ void phys_pair(int h, int pt, int jlat, const double 
         strat1 = pre.strat1;
         ssrd = pre.ssrd;
 #pragma unroll
-        for (int j = 0; j < 4; ++j) rsw[j] = pre.ttrsw[j];
+        for (int j = 0; j < 4; ++j) mh[4 * h + j] = pre.ttrsw[j];
+        SML_PST_T(15, 256);
+        pairx::blackbody(ta, P, st4a1, st4a2);
     }
 
-    SML_PST_T(15, 256);
-    if (lradsw) load_fbq();
-    // 3.2 radlw(-1) (phy_radiat.f90:330-413): the blackbody terms on both lanes, bands
-    // 2h, 2h + 1's downward fluxes after each level
-    double st4a1[NL], st4a2[NL];
-#pragma unroll
-    for (int k = 1; k <= nl1; ++k) st4a1[k - 1] = ta[k - 1] + P->wvi[k - 1][1] * (ta[k] - ta[k - 1]);
-    st4a2[0] = 0.75 * ta[0] + 0.25 * st4a1[0];
-    st4a2[1] = 0.50 * ta[1] + 0.25 * (st4a1[0] + st4a1[1]);
-    {
-        const double anis = 1.0, anish = 0.5 * anis;
-#pragma unroll
-        for (int k = 3; k <= nl1; ++k) st4a2[k - 1] = anish * fmax(st4a1[k - 1] - st4a1[k - 2], 0.);
-        st4a2[NL - 1] = anis * fmax(ta[NL - 1] - st4a1[nl1 - 1], 0.);
-    }
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-        const double x = st4a2[k];
-        st4a1[k] = sbc * ((x * x) * (x * x));
-        st4a2[k] = 0.;
-    }
-#pragma unroll
-    for (int k = 3; k <= NL; ++k) {
-        const double t = ta[k - 1];
-        const double st3a = sbc * (t * t * t);
-        st4a1[k - 1] = st3a * t;
-        st4a2[k - 1] = 4. * st3a * st4a2[k - 1];
-    }
+    // 3.2 radlw(-1) (phy_radiat.f90:330-413): the blackbody terms on both lanes (above; a
+    // shortwave step's in the first stage), bands 2h, 2h + 1's downward fluxes after each level
     double fo[2][NL];  // band 2h + b's flux after level k
 #pragma unroll
     for (int b = 0; b < 2; ++b) {
@@ -365,7 +497,7 @@ __device__ __forceinline__ void phys_pair(int h, int pt, int jlat, const double 
         const double dt1 = P->wvi[nlev - 1][1] * (ta[nlev - 1] - ta[nl1 - 1]);
         t1[0] = ta[nlev - 1] + dt1;
         t1[1] = t1[0] + phi0 * dt1 * rdphi0;
-        t2[1] = ta[nlev - 1] + rcp * ph[nlev - 1];
+        t2[1] = ta[nlev - 1] + rcp * ph7;
         t2[0] = t2[1] - rcp * phi0;
         if (ta[nlev - 1] > ta[nl1 - 1]) {
             t1[0] = ftemp0 * t1[0] + gtemp0 * t2[0];
@@ -488,7 +620,6 @@ __device__ __forceinline__ void phys_pair(int h, int pt, int jlat, const double 
         const double c1 = d - corlw1, c2 = d - corlw2;
         d = L == 0 ? c1 : L == 1 ? c2 : d;
         o.rlw[j] = d * rps * P->grdscp[L];
-        o.rsw[j] = rsw[j];
     }
     o.ust = ustr3;
     o.vst = vstr3;
