@@ -27,11 +27,13 @@
 // host that keeps phypar on the CPU) or are zero.
 #include <hip/hip_runtime.h>
 
+#include <array>
 #include <cmath>
 #include <cstddef>
 #include <cstdlib>
 #include <cstring>
 #include <new>
+#include <utility>
 #include <vector>
 
 #include "sml_dynamics_tables.hpp"
@@ -92,7 +94,7 @@ struct sml_dynamics {
     double *d_vfm = nullptr;  // fused step: m-major forward Fourier coefficients [m][73][lat][2]
     double *d_pfl = nullptr;  // specy's MFMA B operands in lane order [m][k-step][lane][S, D] (k_pack_pfwd)
     double *d_sm = nullptr;   // fused step: m-major state [2][m][var 5][lev 2][kx][n p], ping-pong:
-    int sm_cur = 0;           // k_st_spec reads buffer sm_cur and writes the other (see sm_buf)
+                              // k_st_spec reads one buffer and writes the other (StepCtl::sm, sm_buf)
     long long *d_dbg = nullptr;  // diagnostic phase stamps (SML_DYN_STAMPS=1)
     double *d_tend = nullptr;
     double *d_phys = nullptr;  // physics tendencies: staging for a host's, or the GPU phypar's output
@@ -113,10 +115,16 @@ struct sml_dynamics {
     // sml::dyn_check_late, reset when reported); the exit's give-up time in ticks
     unsigned *d_chk_late = nullptr;
     long long chk_timeout = 100000000ll;
-    // the next run_model's entry waits in-kernel for its input grids (sml::dyn_run_model_wait)
-    HopWait entry_wait;
-    // the next run_model's entry signals its input grid in-kernel (sml::dyn_run_model_entry_signal)
-    uint64_t *entry_sig = nullptr;
+    // one-shot hooks of the next run_model, taken (and so cleared) as it starts; the next
+    // from_grid takes the entry's two
+    struct RunModelHooks {
+        HopWait entry_wait;             // the entry waits in-kernel for its input grids (sml::dyn_run_model_wait)
+        uint64_t *entry_sig = nullptr;  // the entry signals its input grid in-kernel (sml::dyn_run_model_entry_signal)
+        // the exit is followed by a store of exit_store_value to *exit_store
+        // (sml::dyn_run_model_exit_store: the hybrid loop's forecast hop)
+        uint64_t *exit_store = nullptr;
+        uint64_t exit_store_value = 0;
+    } hooks;
     unsigned chk_count = 0;
     bool chk_counted = false;  // the last launch_io_check added to the counter
     // host copy of the last check's min/max (pinned; written behind the check on its
@@ -172,9 +180,8 @@ struct sml_dynamics {
         DynTables *tab[3] = {nullptr, nullptr, nullptr};
         // run_model's exit captured behind the window, and with it the entry (iogrid(30)'s
         // specx + k_io_entry) in front of it: their arguments (the per-launch values come
-        // from d_xa, written before each launch)
-        bool has_exit = false;
-        const void *exit_key[16] = {};
+        // from d_xa, written before each launch); all null without an exit
+        std::array<const void *, 16> exit_key = {};
     };
     // [prepared entry (sml_dyn_run_model)][entry lradsw] x kReplayWays graphs each, so a
     // caller alternating its forecast / input buffers (ping-pong) replays one graph per
@@ -182,10 +189,6 @@ struct sml_dynamics {
     static constexpr int kReplayWays = 4;
     WindowReplay wreplay[4][kReplayWays];
     int wreplay_next[4] = {0, 0, 0, 0};
-    // the next run_model's exit is followed by a store of exit_store_value to
-    // *exit_store (sml::dyn_run_model_exit_store: the hybrid loop's forecast hop)
-    uint64_t *exit_store = nullptr;
-    uint64_t exit_store_value = 0;
     // a graph-captured run_model's per-launch values: [0] the check count the exit waits
     // for, [1] the hop value its store writes, [2] the hop value the entry specx waits for,
     // [3] the window's number, which its first row kernel hands the safety check
@@ -195,16 +198,9 @@ struct sml_dynamics {
     // serialised dispatch): the safety check then waits on its own stream for *d_go >=
     // the window's number, which the window's first row kernel stores as it starts
     // (k_io_entry's outputs are released by then) -- no event fork after k_io_entry
-    bool entry_graph = true;
     bool serialized = false;  // AMD_SERIALIZE_KERNEL / rocprofv3's counter collection at create
     uint64_t *d_go = nullptr;
     uint64_t go_count = 0;
-    // the next fused step's row kernel hands *go_src to *go_dst at its start (one launch)
-    const uint64_t *go_src_next = nullptr;
-    uint64_t *go_dst_next = nullptr;
-    // while a run_model window is captured: the Fourier buffer its last k_st_spec fills
-    // with iogrid(31)'s gridy (spectral layout), else null
-    double *io_exit = nullptr;
 };
 
 namespace {
@@ -2259,11 +2255,30 @@ extern "C" int sml_dyn_state_device(sml_dynamics *d, double **d_state, double **
 
 namespace {
 
+// what one step's launches depend on besides step()'s own arguments
+struct StepCtl {
+    const DynTables *tab;  // the impint slot of the step's (dt, alph)
+    bool lradsw;           // shortwave radiation on this step (GPU physics)
+    // the fused step only.  chained: the previous step's k_st_spec left the m-major state
+    // in buffer sm and this step's gridy output (its next_j2 was this j2), else the step
+    // starts from the reference-layout state; next_j2 > 0: this step's k_st_spec does that
+    // for step (.., next_j2) in buffer 1 - sm, else it writes the reference-layout state
+    bool chained = false;
+    int next_j2 = 0;
+    int sm = 0;
+    // the last step (next_j2 == 0) of a run_model window: the Fourier buffer its k_st_spec
+    // fills with iogrid(31)'s gridy (spectral layout), else null
+    double *io_exit = nullptr;
+    // the row kernel (GPU physics) hands *go_src to *go_dst at its start, or null
+    const uint64_t *go_src = nullptr;
+    uint64_t *go_dst = nullptr;
+};
+
 // the unfused launches of one step(j1, j2, dt, alph, rob, wil) on stream st: 7
 // without GPU physics, 8 with it
 int launch_step_unfused(sml_dynamics *d, int j1, int j2, double dt, double alph, double rob, double wil,
-                        const double *d_phys, bool lradsw, hipStream_t st) {
-    const DynTables *T = d->d_tab;
+                        const double *d_phys, const StepCtl &c, hipStream_t st) {
+    const DynTables *T = c.tab;
     const bool phys = d->phys_on;
     const int n1 = phys ? kNInv1P : kNInv1, nin = phys ? kNInvP : kNInv;
     // 1. grtend: inverse transforms of the j2 state (+ phypar's level-1 inputs)
@@ -2278,7 +2293,7 @@ int launch_step_unfused(sml_dynamics *d, int j1, int j2, double dt, double alph,
         hipLaunchKernelGGL(k_phys, dim3(kNGP / 64), dim3(64), 0, st, G + (size_t)(n1 + 2 * kKX + 2) * kGF,
                            G + (size_t)(n1 + 3 * kKX + 2) * kGF, G + (size_t)kPT1 * kGF, G + (size_t)kPQ1 * kGF,
                            G + (size_t)kPPhi1 * kGF, G + (size_t)kPPs1 * kGF, d->d_pbc, d->d_rad, d->d_ptab,
-                           lradsw ? 1 : 0, d->d_phys);
+                           c.lradsw ? 1 : 0, d->d_phys);
         SML_HIP(hipGetLastError());
         d_phys = d->d_phys;
     }
@@ -2298,37 +2313,34 @@ int launch_step_unfused(sml_dynamics *d, int j1, int j2, double dt, double alph,
     return SML_OK;
 }
 
-// the fused step: [k_state_to_m k_st_inv] (k_st_rows | k_st_gridspec) k_st_spec.
-// chained: the previous launch_step's k_st_spec left the m-major state and this
-// step's gridy output (its next_j2 was this j2); next_j2 > 0: this step's k_st_spec
-// prepares step (.., next_j2) and the state stays m-major, else it writes the
-// reference-layout state.
-
 // buffer b of the m-major state (two, so k_st_spec's second block of an m never
 // reads a slice its lead block already advanced)
 double *sm_buf(sml_dynamics *d, int b) { return d->d_sm + (size_t)b * kMX * kSM; }
 
+// the per-m TabM copies of impint slot T
+const double *tabm_of(const sml_dynamics *d, const DynTables *T) {
+    return d->d_tabm + (size_t)(T - d->d_tabs) * kMX * kTabMDoubles;
+}
+
+// the fused step: [k_state_to_m k_st_inv] (k_st_rows | k_st_gridspec_p) k_st_spec
 int launch_step_fused(sml_dynamics *d, int j1, int j2, double dt, double alph, double rob, double wil,
-                      const double *d_phys, bool lradsw, hipStream_t st, bool chained, int next_j2) {
-    const DynTables *T = d->d_tab;
+                      const double *d_phys, const StepCtl &c, hipStream_t st) {
+    const DynTables *T = c.tab;
     const bool phys = d->phys_on;
     const int n1 = phys ? kNInv1P : kNInv1, nin = phys ? kNInvP : kNInv;
     const SpectralDev sd = spectral_dev(d->sp);
-    if (dt <= 0.0) next_j2 = 0;  // tendencies only: the state does not advance
+    const int next_j2 = dt > 0.0 ? c.next_j2 : 0;  // tendencies only: the state does not advance
     const int conv_blocks = (kMX * kSM + 255) / 256;
-    if (!chained) {  // a chain starts in buffer 0 (so a captured window replays the same pointers)
-        d->sm_cur = 0;
-        hipLaunchKernelGGL(k_state_to_m, dim3(conv_blocks), dim3(256), 0, st, d->d_state, sm_buf(d, 0));
+    if (!c.chained) {
+        hipLaunchKernelGGL(k_state_to_m, dim3(conv_blocks), dim3(256), 0, st, d->d_state, sm_buf(d, c.sm));
         SML_HIP(hipGetLastError());
-        hipLaunchKernelGGL(k_st_inv, dim3(kMX), dim3(kSpecThreads), 0, st, sm_buf(d, 0), d->d_phis, T, sd.pinv,
+        hipLaunchKernelGGL(k_st_inv, dim3(kMX), dim3(kSpecThreads), 0, st, sm_buf(d, c.sm), d->d_phis, T, sd.pinv,
                            d->d_varm, j2, n1, nin);
         SML_HIP(hipGetLastError());
     }
     if (phys) {
         hipLaunchKernelGGL(k_st_gridspec_p, dim3(kIL), dim3(kGpThreads), 0, st, d->d_varm, d->d_vfm, sd.wa, sd.cosgr, T,
-                           d->d_pbc, d->d_rad, d->d_ptab, lradsw ? 1 : 0, d->go_src_next, d->go_dst_next, d->d_dbg);
-        d->go_src_next = nullptr;  // one launch
-        d->go_dst_next = nullptr;
+                           d->d_pbc, d->d_rad, d->d_ptab, c.lradsw ? 1 : 0, c.go_src, c.go_dst, d->d_dbg);
         SML_HIP(hipGetLastError());
     } else {
         hipLaunchKernelGGL(k_st_rows, dim3(kIL), dim3(kRowThreads), 0, st, d->d_varm, d->d_vfm, sd.wa, sd.cosgr, T,
@@ -2336,21 +2348,44 @@ int launch_step_fused(sml_dynamics *d, int j1, int j2, double dt, double alph, d
         SML_HIP(hipGetLastError());
     }
     const int j4 = (alph == 0.0) ? j2 : 1;
-    const int cur = d->sm_cur;
-    if (next_j2 > 0) d->sm_cur = 1 - cur;  // the next step reads what this one writes
     hipLaunchKernelGGL(k_st_spec, dim3(kSpecStride * kSpecSplit), dim3(kSpecBlk), 0, st, d->d_vfm, d->d_pfl, sd.wt,
-                       sm_buf(d, cur), sm_buf(d, 1 - cur), d->d_tend,
+                       sm_buf(d, c.sm), sm_buf(d, 1 - c.sm), d->d_tend,
                        d->d_phi, d->d_phis, d->d_tcorh, d->d_qcorh, T, j1, j4, dt, alph, rob, wil, sd.pinv, d->d_varm,
-                       next_j2, n1, nin, d->d_tabm + (size_t)(d->d_tab - d->d_tabs) * kMX * kTabMDoubles, d->d_state,
-                       next_j2 > 0 ? nullptr : d->io_exit, d->d_dbg);
+                       next_j2, n1, nin, tabm_of(d, T), d->d_state, next_j2 > 0 ? nullptr : c.io_exit, d->d_dbg);
     SML_HIP(hipGetLastError());
     return SML_OK;
 }
 
 int launch_step(sml_dynamics *d, int j1, int j2, double dt, double alph, double rob, double wil, const double *d_phys,
-                bool lradsw, hipStream_t st, bool chained = false, int next_j2 = 0) {
-    return d->fused ? launch_step_fused(d, j1, j2, dt, alph, rob, wil, d_phys, lradsw, st, chained, next_j2)
-                    : launch_step_unfused(d, j1, j2, dt, alph, rob, wil, d_phys, lradsw, st);
+                const StepCtl &c, hipStream_t st) {
+    return d->fused ? launch_step_fused(d, j1, j2, dt, alph, rob, wil, d_phys, c, st)
+                    : launch_step_unfused(d, j1, j2, dt, alph, rob, wil, d_phys, c, st);
+}
+
+// what body(stream) enqueues, captured and instantiated as *out in place of the graph
+// there (null on an error); what: the caller's name for the messages
+template <class Body>
+int capture_graph(sml_dynamics *d, const char *what, Body body, hipGraphExec_t *out) {
+    if (*out) {
+        SML_HIP(hipGraphExecDestroy(*out));
+        *out = nullptr;
+    }
+    if (!d->cap_stream) SML_HIP(hipStreamCreateWithFlags(&d->cap_stream, hipStreamNonBlocking));
+    hipGraph_t g = nullptr;
+    SML_HIP(hipStreamBeginCapture(d->cap_stream, hipStreamCaptureModeThreadLocal));
+    const int rc = body(d->cap_stream);
+    hipError_t e = hipStreamEndCapture(d->cap_stream, &g);  // whatever rc: the stream leaves capture mode
+    if (rc || e != hipSuccess) {
+        if (g) (void)hipGraphDestroy(g);
+        return rc ? rc : fail(SML_ERR_HIP, "%s capture: %s", what, hipGetErrorString(e));
+    }
+    e = hipGraphInstantiate(out, g, nullptr, nullptr, 0);
+    (void)hipGraphDestroy(g);
+    if (e != hipSuccess) {
+        *out = nullptr;
+        return fail(SML_ERR_HIP, "%s instantiate: %s", what, hipGetErrorString(e));
+    }
+    return SML_OK;
 }
 
 }  // namespace
@@ -2361,7 +2396,7 @@ extern "C" int sml_dyn_step(sml_dynamics *d, int j1, int j2, double dt, double a
     SML_REQUIRE((j1 == 1 || j1 == 2) && (j2 == 1 || j2 == 2), "j1/j2 must be 1 or 2");
     SML_REQUIRE(!(d->phys_on && d_phys), "physics runs on the GPU (sml_dyn_set_physics): d_phys must be NULL");
     if (!d->impint_done) return fail(SML_ERR_STATE, "sml_dyn_impint must be called before sml_dyn_step");
-    return launch_step(d, j1, j2, dt, alph, rob, wil, d_phys, d->lradsw, (hipStream_t)stream);
+    return launch_step(d, j1, j2, dt, alph, rob, wil, d_phys, StepCtl{d->d_tab, d->lradsw}, (hipStream_t)stream);
 }
 
 namespace {
@@ -2374,26 +2409,12 @@ int leapfrog_graph(sml_dynamics *d, bool lradsw, const double key[4], const doub
         *out = r.exec;
         return SML_OK;
     }
-    if (r.exec) {
-        SML_HIP(hipGraphExecDestroy(r.exec));
-        r.exec = nullptr;
-    }
-    if (!d->cap_stream) SML_HIP(hipStreamCreateWithFlags(&d->cap_stream, hipStreamNonBlocking));
-    hipGraph_t g = nullptr;
-    SML_HIP(hipStreamBeginCapture(d->cap_stream, hipStreamCaptureModeThreadLocal));
-    int rc = launch_step(d, 2, 2, key[0], key[1], key[2], key[3], d_phys, lradsw, d->cap_stream);
-    hipError_t e = hipStreamEndCapture(d->cap_stream, &g);
-    if (rc) {
-        if (g) (void)hipGraphDestroy(g);
+    const StepCtl c{d->d_tab, lradsw};
+    if (int rc = capture_graph(
+            d, "sml_dyn_leapfrog",
+            [&](hipStream_t st) { return launch_step(d, 2, 2, key[0], key[1], key[2], key[3], d_phys, c, st); },
+            &r.exec))
         return rc;
-    }
-    if (e != hipSuccess) return fail(SML_ERR_HIP, "sml_dyn_leapfrog capture: %s", hipGetErrorString(e));
-    e = hipGraphInstantiate(&r.exec, g, nullptr, nullptr, 0);
-    (void)hipGraphDestroy(g);
-    if (e != hipSuccess) {
-        r.exec = nullptr;
-        return fail(SML_ERR_HIP, "sml_dyn_leapfrog instantiate: %s", hipGetErrorString(e));
-    }
     std::memcpy(r.key, key, sizeof r.key);
     r.phys = d_phys;
     r.tab = d->d_tab;
@@ -2422,14 +2443,90 @@ extern "C" int sml_dyn_leapfrog(sml_dynamics *d, int nsteps, double dt, double a
     return SML_OK;
 }
 
+namespace {
+// the safety check of iogrid(30) (ppo_iogrid.f90:556-571) from its spectral inputs in
+// d_chk (k_io_prep / k_io_entry, already on st): the re-grid and its min / max run on
+// chk_stream beside the window.  A caller's d_minmax is ready in st's order; the
+// internal one (nullptr) only for the next user of d_chk (which waits for it).
+// go > 0 (the entry inside the window graph): instead of an event fork from st, the
+// check's stream waits in-kernel for the window's first row kernel to store go
+int launch_io_check(sml_dynamics *d, hipStream_t st, double *d_minmax, uint64_t go = 0) {
+    double *cs = d->d_chk, *cv = cs + (size_t)kNIo * kSF, *cg = cv + (size_t)kNIo * kVF;
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    SML_HIP(hipStreamIsCapturing(st, &cap));
+    hipStream_t cst = st;
+    if (cap == hipStreamCaptureStatusNone) {
+        if (!d->chk_stream) {
+            SML_HIP(hipStreamCreateWithFlags(&d->chk_stream, hipStreamNonBlocking));
+            SML_HIP(hipEventCreateWithFlags(&d->ev_fork, hipEventDisableTiming));
+            SML_HIP(hipEventCreateWithFlags(&d->ev_chk, hipEventDisableTiming));
+        }
+        cst = d->chk_stream;
+        if (go) {
+            hipLaunchKernelGGL(k_check_go, dim3(1), dim3(64), 0, cst, d->d_go, go, d->d_chk_late,
+                               4u * (d->chk_count + 1), d->chk_timeout);
+            SML_HIP(hipGetLastError());
+        } else {
+            SML_HIP(hipEventRecord(d->ev_fork, st));
+            SML_HIP(hipStreamWaitEvent(d->chk_stream, d->ev_fork, 0));
+        }
+    } else if (go) {
+        return fail(SML_ERR_STATE, "launch_io_check: a go hand-off while the stream is captured");
+    }
+    if (int rc = spectral_gridy(d->sp, cs, cv, kNIo, cst)) return rc;
+    if (int rc = spectral_gridx_range(d->sp, cv, cg, kNIo, 0, kNIoWind, cst)) return rc;
+    double *mm = d_minmax ? d_minmax : d->d_minmax;
+    // on the check stream, for run_model's exit: the counter hand-off (4 adds per check)
+    const bool counted = cst != st && !d_minmax;
+    hipLaunchKernelGGL(k_io_minmax, dim3(4), dim3(1024), 0, cst, cg, mm, counted ? d->d_chk_cnt : nullptr,
+                       go ? d->d_chk_late : nullptr, 4u * (d->chk_count + 1));
+    SML_HIP(hipGetLastError());
+    if (counted) ++d->chk_count;
+    d->chk_counted = counted;
+    d->mm_last = mm;
+    d->mm_issued = false;
+    if (cst != st) {  // a host copy for sml_dyn_last_safe, behind the check on its stream
+        if (!d->h_mm) {
+            SML_HIP(hipHostMalloc((void **)&d->h_mm, 8 * sizeof(double), hipHostMallocDefault));
+            SML_HIP(hipEventCreateWithFlags(&d->ev_mm, hipEventDisableTiming));
+        }
+        SML_HIP(hipMemcpyAsync(d->h_mm, mm, 8 * sizeof(double), hipMemcpyDeviceToHost, cst));
+        SML_HIP(hipEventRecord(d->ev_mm, cst));
+        d->mm_issued = true;
+        SML_HIP(hipEventRecord(d->ev_chk, cst));
+        d->chk_pending = true;
+        if (d_minmax) {
+            SML_HIP(hipStreamWaitEvent(st, d->ev_chk, 0));
+            d->chk_pending = false;
+        }
+    }
+    return SML_OK;
+}
+
+// run_model's entry: iogrid(30)'s specx (waiting for its grid when w.flag) and the per-m
+// k_io_entry (specy, the combine into level 1 with impint slot T's tables, the check's
+// inputs, the m-major state in buffer 0, step(1, 1)'s gridy); xa: an exit captured in the
+// window graph takes its per-launch values from there (k_io_entry stores xa0 / xa1), else null
+int launch_entry(sml_dynamics *d, const DynTables *T, const double *d_grid4d, const double *d_logp, HopWait w,
+                 hipStream_t st, uint64_t *xa, uint64_t xa0, uint64_t xa1) {
+    if (int rc = spectral_specx_io(d->sp, d_grid4d, d_logp, d->d_vfm, kNIoWind, st, w)) return rc;
+    const SpectralDev sd = spectral_dev(d->sp);
+    const bool phys = d->phys_on;
+    hipLaunchKernelGGL(k_io_entry, dim3(kMX), dim3(kSpecThreads), 0, st, d->d_vfm, d->d_pfl, sd.wt, d->d_state,
+                       sm_buf(d, 0), d->d_chk, d->d_phis, tabm_of(d, T), sd.pinv, d->d_varm,
+                       phys ? kNInv1P : kNInv1, phys ? kNInvP : kNInv, xa, xa0, xa1);
+    SML_HIP(hipGetLastError());
+    return SML_OK;
+}
+
 // One SPEEDY window after iogrid(30): stepone (ini_stepone.f90:19-34: step(1, 1,
 // delt/2), step(1, 2, delt) with the lradsw the previous window left) and nleap x
 // step(2, 2, 2 delt) with stloop's radiation clock restarted at istep = 1
 // (dyn_stloop.f90:37-56, at_gcm.f90:81), captured once as ONE hipGraph per
 // (entry lradsw, delt, alph, rob, wil, physics on, impint slots) and replayed with
 // a single launch, so the host thread never waits on the window's ~200 kernels.
-namespace {
-// run_model's exit as window_impl captures it behind the window: iogrid(31)'s gridx
+
+// run_model's exit as enqueue_window issues it behind the window: iogrid(31)'s gridx
 // (IoExit) and an optional one-lane store (the hybrid loop's forecast hop)
 // and, with `entry`, run_model's entry in front of the window: iogrid(30)'s specx (its
 // hop wait's value from d_xa) and k_io_entry, the first row kernel handing *go_src to the
@@ -2445,71 +2542,82 @@ struct ExitSpec {
     double *fc4, *fc2;
     IoExit ex;
     uint64_t *store;
-    uint64_t store_value;
-    const EntrySpec *entry = nullptr;
+    const EntrySpec *entry;
 };
-int launch_entry(sml_dynamics *d, const double *d_grid4d, const double *d_logp, HopWait w, hipStream_t st,
-                 uint64_t *xa, uint64_t xa0, uint64_t xa1);
-int window_impl(sml_dynamics *d, int nleap, double delt, double alph, double rob, double wil, void *stream,
-                bool prepared, const ExitSpec *exit = nullptr);
-}  // namespace
+struct WindowPlan {
+    int nleap;
+    double dts[3];  // delt / 2, delt, 2 delt
+    double alph, rob, wil;
+    DynTables *tab[3];  // their impint slots (4 cached slots hold all three tables at once)
+    bool lradsw;        // stepone's: what the previous window left
+    // prepared: the m-major state and step(1, 1)'s gridy output are already in place
+    // (k_io_entry, fused path of sml_dyn_run_model), so the window starts at the row
+    // kernel of the first step and its last kernel does iogrid(31)'s gridy
+    bool prepared;
+    const ExitSpec *exit;  // or null
+};
 
-extern "C" int sml_dyn_window(sml_dynamics *d, int nleap, double delt, double alph, double rob, double wil,
-                              void *stream) {
-    SML_REQUIRE(d && nleap >= 0 && delt > 0.0, "bad argument");
-    return window_impl(d, nleap, delt, alph, rob, wil, stream, false);
+// the window's launches on st: [entry] step(1, 1) step(1, 2) nleap x step(2, 2) [exit [store]]
+int enqueue_window(sml_dynamics *d, hipStream_t st, const WindowPlan &p) {
+    StepCtl c{p.tab[0], p.lradsw, p.prepared};
+    c.io_exit = p.prepared ? d->d_varm : nullptr;
+    if (p.exit && p.exit->entry) {
+        // (with the tables the entry read when it was launched before the graph: the
+        // last impint's, 2 delt, as the previous window left them)
+        const EntrySpec *en = p.exit->entry;
+        if (int rc = launch_entry(d, p.tab[2], en->g4, en->logp, en->w, st, nullptr, 0, 0)) return rc;
+        c.go_src = en->go_src;  // the first row kernel lets the safety check go
+        c.go_dst = en->go;
+    }
+    // consecutive steps chained: each step's last kernel prepares the next one's inverse
+    // transforms (j2 = 1 for step(1, 1), then 2) in the other m-major buffer
+    auto step = [&](int j1, int j2, int i, bool last) {
+        c.tab = p.tab[i];
+        c.next_j2 = last ? 0 : 2;
+        const int rc = launch_step(d, j1, j2, p.dts[i], p.alph, p.rob, p.wil, nullptr, c, st);
+        c.chained = true;
+        if (!last) c.sm = 1 - c.sm;
+        c.go_src = nullptr;
+        c.go_dst = nullptr;
+        return rc;
+    };
+    if (int rc = step(1, 1, 0, false)) return rc;
+    if (int rc = step(1, 2, 1, p.nleap == 0)) return rc;
+    for (int i = 0; i < p.nleap; ++i) {
+        c.lradsw = (1 + i) % kNstrad == 1;
+        if (int rc = step(2, 2, 2, i + 1 == p.nleap)) return rc;
+    }
+    if (const ExitSpec *x = p.exit) {  // iogrid(31)'s gridx and the hop's store behind the window
+        if (int rc = spectral_gridx_run_model_exit(d->sp, x->varm, x->fc4, x->fc2, kNIoWind, x->ex, st)) return rc;
+        if (x->store) {
+            hipLaunchKernelGGL(k_flag_store, dim3(1), dim3(64), 0, st, x->store, x->ex.xa);
+            SML_HIP(hipGetLastError());
+        }
+    }
+    return SML_OK;
 }
 
-namespace {
-// prepared: the m-major state and step(1, 1)'s gridy output are already in place
-// (k_io_entry, fused path of sml_dyn_run_model), so the graph starts at the row
-// kernel of the first step
-int window_impl(sml_dynamics *d, int nleap, double delt, double alph, double rob, double wil, void *stream,
-                bool prepared, const ExitSpec *exit) {
-    const double dts[3] = {0.5 * delt, delt, 2.0 * delt};
-    DynTables *tab[3];
-    for (int i = 0; i < 3; ++i) {  // 4 cached slots hold all three tables at once
-        if (int rc = sml_dyn_impint(d, dts[i], alph)) return rc;
-        tab[i] = d->d_tab;
-    }
-    const bool entry = d->lradsw;
-    if (d->nograph) {  // the same launches, issued one by one on the stream (A/B: SML_DYN_NOGRAPH=1)
-        hipStream_t st = (hipStream_t)stream;
-        d->d_tab = tab[0];
-        d->io_exit = prepared ? d->d_varm : nullptr;
-        int rc = launch_step(d, 1, 1, dts[0], alph, rob, wil, nullptr, entry, st, prepared, 2);
-        d->d_tab = tab[1];
-        if (!rc) rc = launch_step(d, 1, 2, dts[1], alph, rob, wil, nullptr, entry, st, true, nleap > 0 ? 2 : 0);
-        d->d_tab = tab[2];
-        for (int i = 0; i < nleap && !rc; ++i)
-            rc = launch_step(d, 2, 2, dts[2], alph, rob, wil, nullptr, (1 + i) % kNstrad == 1, st, true,
-                             i + 1 < nleap ? 2 : 0);
-        d->io_exit = nullptr;
-        if (rc) return rc;
-        d->istep = 1 + nleap;
-        if (nleap > 0) d->lradsw = (nleap % kNstrad == 1);
-        return SML_OK;
-    }
-    const int cls = (entry ? 1 : 0) + (prepared ? 2 : 0);
-    const double key[8] = {(double)nleap, delt,  alph, rob, wil, d->phys_on ? 1.0 : 0.0, d->fused ? 1.0 : 0.0,
-                           prepared ? 2.0 : 1.0};
+// the graph of p's launches: replayed, or captured into its class's next way
+int window_graph(sml_dynamics *d, const WindowPlan &p, hipGraphExec_t *out) {
+    const ExitSpec *exit = p.exit;
+    const int cls = (p.lradsw ? 1 : 0) + (p.prepared ? 2 : 0);
+    const double key[8] = {(double)p.nleap,      p.dts[1], p.alph, p.rob, p.wil, d->phys_on ? 1.0 : 0.0,
+                           d->fused ? 1.0 : 0.0, p.prepared ? 2.0 : 1.0};
     // the exit's (and entry's) fixed arguments (the counts and hop values change per
-    // launch: d_xa)
-    const void *exit_key[16] = {};
+    // launch: d_xa); varm is never null, so no window without an exit has this key
+    std::array<const void *, 16> exit_key = {};
     if (exit) {
         const EntrySpec *en = exit->entry;
-        const void *k[16] = {exit->varm,   exit->fc4,     exit->fc2,    exit->ex.mm,
-                             exit->ex.in4, exit->ex.inlp, exit->ex.cnt, (const void *)(intptr_t)exit->ex.timeout,
-                             exit->store,  en ? (const void *)1 : nullptr,
-                             en ? en->w.flag : nullptr, en ? en->w.late : nullptr, en ? en->w.sig : nullptr,
-                             en ? (const void *)(intptr_t)en->w.timeout : nullptr, en ? en->w.vptr : nullptr,
-                             en ? en->go : nullptr};
-        std::memcpy(exit_key, k, sizeof k);
+        exit_key = {exit->varm,   exit->fc4,     exit->fc2,    exit->ex.mm,
+                    exit->ex.in4, exit->ex.inlp, exit->ex.cnt, (const void *)(intptr_t)exit->ex.timeout,
+                    exit->store,  en ? (const void *)1 : nullptr,
+                    en ? en->w.flag : nullptr, en ? en->w.late : nullptr, en ? en->w.sig : nullptr,
+                    en ? (const void *)(intptr_t)en->w.timeout : nullptr, en ? en->w.vptr : nullptr,
+                    en ? en->go : nullptr};
     }
     auto same = [&](const sml_dynamics::WindowReplay &w) {
-        return w.exec && w.has_exit == (exit != nullptr) &&
-               (!exit || std::memcmp(exit_key, w.exit_key, sizeof exit_key) == 0) &&
-               std::memcmp(key, w.key, sizeof key) == 0 && std::memcmp(tab, w.tab, sizeof tab) == 0;
+        return w.exec && exit_key == w.exit_key &&
+               std::memcmp(key, w.key, sizeof key) == 0 && std::memcmp(p.tab, w.tab, sizeof p.tab) == 0;
     };
     sml_dynamics::WindowReplay *hit = nullptr;
     for (auto &w : d->wreplay[cls])
@@ -2517,73 +2625,44 @@ int window_impl(sml_dynamics *d, int nleap, double delt, double alph, double rob
     if (!hit) {  // capture into the class's next way
         hit = &d->wreplay[cls][d->wreplay_next[cls]];
         d->wreplay_next[cls] = (d->wreplay_next[cls] + 1) % sml_dynamics::kReplayWays;
-    }
-    sml_dynamics::WindowReplay &r = *hit;
-    if (!same(r)) {
-        if (r.exec) {
-            SML_HIP(hipGraphExecDestroy(r.exec));
-            r.exec = nullptr;
-        }
-        r.has_exit = false;
-        if (!d->cap_stream) SML_HIP(hipStreamCreateWithFlags(&d->cap_stream, hipStreamNonBlocking));
-        hipGraph_t g = nullptr;
-        SML_HIP(hipStreamBeginCapture(d->cap_stream, hipStreamCaptureModeThreadLocal));
-        // consecutive steps chained: each step's last kernel prepares the next one's
-        // inverse transforms (j2 = 1 for step(1, 1), then 2)
-        int rc = SML_OK;
-        if (exit && exit->entry) {  // run_model's entry (specx + k_io_entry) in front of the window
-            // (with the tables the entry read when it was launched before the graph: the
-            // last impint's, 2 delt, as the previous window left them)
-            const EntrySpec *en = exit->entry;
-            rc = launch_entry(d, en->g4, en->logp, en->w, d->cap_stream, nullptr, 0, 0);
-            d->go_src_next = en->go_src;  // the first row kernel lets the safety check go
-            d->go_dst_next = en->go;
-        }
-        d->d_tab = tab[0];
-        d->io_exit = prepared ? d->d_varm : nullptr;  // run_model: the exit's gridy in the last kernel
-        if (!rc) rc = launch_step(d, 1, 1, dts[0], alph, rob, wil, nullptr, entry, d->cap_stream, prepared, 2);
-        d->go_src_next = nullptr;
-        d->go_dst_next = nullptr;
-        d->d_tab = tab[1];
-        if (!rc) rc = launch_step(d, 1, 2, dts[1], alph, rob, wil, nullptr, entry, d->cap_stream, true, nleap > 0 ? 2 : 0);
-        d->d_tab = tab[2];
-        for (int i = 0; i < nleap && !rc; ++i)
-            rc = launch_step(d, 2, 2, dts[2], alph, rob, wil, nullptr, (1 + i) % kNstrad == 1, d->cap_stream, true,
-                             i + 1 < nleap ? 2 : 0);
-        if (!rc && exit) {  // iogrid(31)'s gridx and the hop's store behind the window
-            rc = spectral_gridx_run_model_exit(d->sp, exit->varm, exit->fc4, exit->fc2, kNIoWind, exit->ex,
-                                               d->cap_stream);
-            if (!rc && exit->store) {
-                hipLaunchKernelGGL(k_flag_store, dim3(1), dim3(64), 0, d->cap_stream, exit->store, exit->ex.xa);
-                if (hipGetLastError() != hipSuccess) rc = fail(SML_ERR_HIP, "k_flag_store capture");
-            }
-        }
-        hipError_t e = hipStreamEndCapture(d->cap_stream, &g);
-        d->io_exit = nullptr;
-        if (rc) {
-            if (g) (void)hipGraphDestroy(g);
+        sml_dynamics::WindowReplay &r = *hit;
+        if (int rc = capture_graph(
+                d, "sml_dyn_window", [&](hipStream_t st) { return enqueue_window(d, st, p); }, &r.exec))
             return rc;
-        }
-        if (e != hipSuccess) return fail(SML_ERR_HIP, "sml_dyn_window capture: %s", hipGetErrorString(e));
-        e = hipGraphInstantiate(&r.exec, g, nullptr, nullptr, 0);
-        if (e != hipSuccess) {
-            (void)hipGraphDestroy(g);
-            r.exec = nullptr;
-            return fail(SML_ERR_HIP, "sml_dyn_window instantiate: %s", hipGetErrorString(e));
-        }
-        (void)hipGraphDestroy(g);
-        r.has_exit = exit != nullptr;
-        std::memcpy(r.exit_key, exit_key, sizeof exit_key);
+        r.exit_key = exit_key;
         std::memcpy(r.key, key, sizeof key);
-        std::memcpy(r.tab, tab, sizeof tab);
+        std::memcpy(r.tab, p.tab, sizeof p.tab);
     }
-    SML_HIP(hipGraphLaunch(r.exec, (hipStream_t)stream));
-    d->d_tab = tab[2];
+    *out = hit->exec;
+    return SML_OK;
+}
+
+int window_impl(sml_dynamics *d, int nleap, double delt, double alph, double rob, double wil, hipStream_t st,
+                bool prepared, const ExitSpec *exit = nullptr) {
+    WindowPlan p{nleap, {0.5 * delt, delt, 2.0 * delt}, alph, rob, wil, {}, d->lradsw, prepared, exit};
+    for (int i = 0; i < 3; ++i) {
+        if (int rc = sml_dyn_impint(d, p.dts[i], alph)) return rc;
+        p.tab[i] = d->d_tab;
+    }
+    if (d->nograph) {  // the same launches, issued one by one on the stream (A/B: SML_DYN_NOGRAPH=1)
+        if (int rc = enqueue_window(d, st, p)) return rc;
+    } else {
+        hipGraphExec_t exec = nullptr;
+        if (int rc = window_graph(d, p, &exec)) return rc;
+        SML_HIP(hipGraphLaunch(exec, st));
+    }
+    d->d_tab = p.tab[2];
     d->istep = 1 + nleap;
     if (nleap > 0) d->lradsw = (nleap % kNstrad == 1);
     return SML_OK;
 }
 }  // namespace
+
+extern "C" int sml_dyn_window(sml_dynamics *d, int nleap, double delt, double alph, double rob, double wil,
+                              void *stream) {
+    SML_REQUIRE(d && nleap >= 0 && delt > 0.0, "bad argument");
+    return window_impl(d, nleap, delt, alph, rob, wil, (hipStream_t)stream, false);
+}
 
 extern "C" int sml_dyn_set_clock(sml_dynamics *d, int istep, int lradsw) {
     SML_REQUIRE(d, "null context");
@@ -2951,103 +3030,21 @@ extern "C" int sml_phys_sflset(const double *phi0, double *forog) {
 }
 
 namespace {
-
-// iogrid inverse half: level 1 -> G = [u 8 | v 8 | t 8 | q 8 | ps] grids
-}  // namespace
-
-namespace {
-// the safety check of iogrid(30) (ppo_iogrid.f90:556-571) from its spectral inputs in
-// d_chk (k_io_prep / k_io_entry, already on st): the re-grid and its min / max run on
-// chk_stream beside the window.  A caller's d_minmax is ready in st's order; the
-// internal one (nullptr) only for the next user of d_chk (which waits for it).
-// go > 0 (the entry inside the window graph): instead of an event fork from st, the
-// check's stream waits in-kernel for the window's first row kernel to store go
-int launch_io_check(sml_dynamics *d, hipStream_t st, double *d_minmax, uint64_t go = 0) {
-    double *cs = d->d_chk, *cv = cs + (size_t)kNIo * kSF, *cg = cv + (size_t)kNIo * kVF;
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    SML_HIP(hipStreamIsCapturing(st, &cap));
-    hipStream_t cst = st;
-    if (cap == hipStreamCaptureStatusNone) {
-        if (!d->chk_stream) {
-            SML_HIP(hipStreamCreateWithFlags(&d->chk_stream, hipStreamNonBlocking));
-            SML_HIP(hipEventCreateWithFlags(&d->ev_fork, hipEventDisableTiming));
-            SML_HIP(hipEventCreateWithFlags(&d->ev_chk, hipEventDisableTiming));
-        }
-        cst = d->chk_stream;
-        if (go) {
-            hipLaunchKernelGGL(k_check_go, dim3(1), dim3(64), 0, cst, d->d_go, go, d->d_chk_late,
-                               4u * (d->chk_count + 1), d->chk_timeout);
-            SML_HIP(hipGetLastError());
-        } else {
-            SML_HIP(hipEventRecord(d->ev_fork, st));
-            SML_HIP(hipStreamWaitEvent(d->chk_stream, d->ev_fork, 0));
-        }
-    } else if (go) {
-        return fail(SML_ERR_STATE, "launch_io_check: a go hand-off while the stream is captured");
-    }
-    if (int rc = spectral_gridy(d->sp, cs, cv, kNIo, cst)) return rc;
-    if (int rc = spectral_gridx_range(d->sp, cv, cg, kNIo, 0, kNIoWind, cst)) return rc;
-    double *mm = d_minmax ? d_minmax : d->d_minmax;
-    // on the check stream, for run_model's exit: the counter hand-off (4 adds per check)
-    const bool counted = cst != st && !d_minmax;
-    hipLaunchKernelGGL(k_io_minmax, dim3(4), dim3(1024), 0, cst, cg, mm, counted ? d->d_chk_cnt : nullptr,
-                       go ? d->d_chk_late : nullptr, 4u * (d->chk_count + 1));
-    SML_HIP(hipGetLastError());
-    if (counted) ++d->chk_count;
-    d->chk_counted = counted;
-    d->mm_last = mm;
-    d->mm_issued = false;
-    if (cst != st) {  // a host copy for sml_dyn_last_safe, behind the check on its stream
-        if (!d->h_mm) {
-            SML_HIP(hipHostMalloc((void **)&d->h_mm, 8 * sizeof(double), hipHostMallocDefault));
-            SML_HIP(hipEventCreateWithFlags(&d->ev_mm, hipEventDisableTiming));
-        }
-        SML_HIP(hipMemcpyAsync(d->h_mm, mm, 8 * sizeof(double), hipMemcpyDeviceToHost, cst));
-        SML_HIP(hipEventRecord(d->ev_mm, cst));
-        d->mm_issued = true;
-        SML_HIP(hipEventRecord(d->ev_chk, cst));
-        d->chk_pending = true;
-        if (d_minmax) {
-            SML_HIP(hipStreamWaitEvent(st, d->ev_chk, 0));
-            d->chk_pending = false;
-        }
-    }
-    return SML_OK;
-}
-
-// run_model's entry: iogrid(30)'s specx (waiting for its grid when w.flag) and the per-m
-// k_io_entry (specy, the combine into level 1, the check's inputs, the m-major state,
-// step(1, 1)'s gridy); xa: an exit captured in the window graph takes its per-launch
-// values from there (k_io_entry stores xa0 / xa1), else null
-int launch_entry(sml_dynamics *d, const double *d_grid4d, const double *d_logp, HopWait w, hipStream_t st,
-                 uint64_t *xa, uint64_t xa0, uint64_t xa1) {
-    if (int rc = spectral_specx_io(d->sp, d_grid4d, d_logp, d->d_vfm, kNIoWind, st, w)) return rc;
-    const SpectralDev sd = spectral_dev(d->sp);
-    const bool phys = d->phys_on;
-    hipLaunchKernelGGL(k_io_entry, dim3(kMX), dim3(kSpecThreads), 0, st, d->d_vfm, d->d_pfl, sd.wt, d->d_state,
-                       sm_buf(d, 0), d->d_chk, d->d_phis,
-                       d->d_tabm + (size_t)(d->d_tab - d->d_tabs) * kMX * kTabMDoubles, sd.pinv, d->d_varm,
-                       phys ? kNInv1P : kNInv1, phys ? kNInvP : kNInv, xa, xa0, xa1);
-    SML_HIP(hipGetLastError());
-    return SML_OK;
-}
-}  // namespace
-
-extern "C" int sml_dyn_from_grid(sml_dynamics *d, const double *d_grid4d, const double *d_logp, double *d_minmax,
-                                 void *stream) {
-    SML_REQUIRE(d && d_grid4d && d_logp, "null argument");
-    hipStream_t st = (hipStream_t)stream;
-    const DynTables *T = d->d_tab;
-    if (d->chk_pending) {  // the previous check still reads d_chk
+// the previous safety check still reads d_chk / writes its min/max: st waits for it
+int wait_pending_check(sml_dynamics *d, hipStream_t st) {
+    if (d->chk_pending) {
         SML_HIP(hipStreamWaitEvent(st, d->ev_chk, 0));
         d->chk_pending = false;
     }
+    return SML_OK;
+}
+
+// iogrid(30) with the entry specx's hop wait / signal w
+int from_grid(sml_dynamics *d, const double *d_grid4d, const double *d_logp, double *d_minmax, hipStream_t st,
+              HopWait w) {
+    const DynTables *T = d->d_tab;
     // entry (:503-518): real(4) copies, q clip, then vdspec kcos = 2 (x cosgr) on the
     // winds and none on the rest: one specx launch reading variables3d / logp
-    HopWait w = d->entry_wait;
-    w.sig = d->entry_sig;
-    d->entry_wait = HopWait{};  // one launch
-    d->entry_sig = nullptr;
     if (int rc = spectral_specx_io(d->sp, d_grid4d, d_logp, d->d_varm, kNIoWind, st, w)) return rc;
     if (int rc = spectral_specy(d->sp, d->d_varm, d->d_sfwd, kNIo, st)) return rc;
     hipLaunchKernelGGL(k_io_combine, dim3((kMN + 127) / 128, kKX), dim3(128), 0, st, d->d_sfwd, d->d_state, T);
@@ -3057,6 +3054,17 @@ extern "C" int sml_dyn_from_grid(sml_dynamics *d, const double *d_grid4d, const 
     hipLaunchKernelGGL(k_io_prep, dim3((kMN + 127) / 128, kKX), dim3(128), 0, st, d->d_state, d->d_chk, T);
     SML_HIP(hipGetLastError());
     return launch_io_check(d, st, d_minmax);
+}
+}  // namespace
+
+extern "C" int sml_dyn_from_grid(sml_dynamics *d, const double *d_grid4d, const double *d_logp, double *d_minmax,
+                                 void *stream) {
+    SML_REQUIRE(d && d_grid4d && d_logp, "null argument");
+    hipStream_t st = (hipStream_t)stream;
+    if (int rc = wait_pending_check(d, st)) return rc;
+    HopWait w = std::exchange(d->hooks.entry_wait, HopWait{});  // one launch
+    w.sig = std::exchange(d->hooks.entry_sig, nullptr);
+    return from_grid(d, d_grid4d, d_logp, d_minmax, st, w);
 }
 
 extern "C" int sml_dyn_to_grid(sml_dynamics *d, double *d_grid4d, double *d_logp, void *stream) {
@@ -3075,6 +3083,27 @@ extern "C" int sml_dyn_is_safe(const double *minmax) {
     return io_state_safe(minmax) ? 1 : 0;  // u, v, t, q thresholds (ppo_iogrid.f90:563-577)
 }
 
+namespace {
+// run_model's exit arguments: the q floor, the check's min/max (run_model's checks all
+// write d_minmax) and the window's input grids.  counted: the exit kernel itself waits for
+// the check's counter, so no event wait (a barrier packet with a cross-queue dependency)
+// on the window's stream; the count to reach is `target`, or xa[0] (and target 0) for an
+// exit replayed inside a graph (its arguments are fixed).  The check is complete once such
+// an exit has run, so the next user of d_chk needs no wait either
+IoExit run_model_exit(const sml_dynamics *d, const double *d_grid4d, const double *d_logp, bool counted,
+                      unsigned target, const uint64_t *xa) {
+    IoExit ex{0.000001, d->d_minmax, d_grid4d, d_logp};
+    if (counted) {
+        ex.cnt = d->d_chk_cnt;
+        ex.late = d->d_chk_late;
+        ex.timeout = d->chk_timeout;
+        ex.target = target;
+        ex.xa = xa;
+    }
+    return ex;
+}
+}  // namespace
+
 // run_model (src/mpires.f90:1516-1628) on the device: agcm_main's window entry
 // iogrid(30) with its safety check, the window (integrated whatever the check says:
 // the outcome is selected at the exit), iogrid(31), then run_model's q floor; when
@@ -3088,109 +3117,88 @@ extern "C" int sml_dyn_run_model(sml_dynamics *d, const double *d_grid4d, const 
     SML_REQUIRE(d_fc4d != d_grid4d && d_fc2d != d_logp, "the forecast must not overwrite the window's input");
     SML_REQUIRE(nleap >= 0 && delt > 0.0, "bad argument");
     hipStream_t st = (hipStream_t)stream;
-    if (d->fused) {
-        // iogrid(30)'s specx, then ONE per-m launch for specy, the combine into level 1,
-        // the check's inputs, the m-major state and step(1, 1)'s gridy (k_io_entry);
-        // the window graph then starts at the first row kernel
-        if (d->chk_pending) {
-            SML_HIP(hipStreamWaitEvent(st, d->ev_chk, 0));
-            d->chk_pending = false;
+    if (int rc = wait_pending_check(d, st)) return rc;
+    const sml_dynamics::RunModelHooks h = std::exchange(d->hooks, {});  // one launch
+    HopWait w = h.entry_wait;
+    w.sig = h.entry_sig;
+    // The fused form: iogrid(30)'s specx, then ONE per-m launch for specy, the combine
+    // into level 1, the check's inputs, the m-major state and step(1, 1)'s gridy
+    // (k_io_entry); the window then starts at the first row kernel.
+    // The exit inside the window graph: needs the check's counter hand-off (no event
+    // wait between the window and the exit; the check counts unless captured) and the
+    // graph path.  Its per-launch values go through d_xa.
+    // And the entry inside it too (r06): specx + k_io_entry as the graph's first nodes,
+    // the safety check forked by the first row kernel's go store instead of an event
+    // after k_io_entry -- one launch boundary fewer on the chain, and the graph's launch
+    // hidden behind the entry's wait.  Not under serialised dispatch (the check, enqueued
+    // after the graph, would run after the exit that waits for it)
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    SML_HIP(hipStreamIsCapturing(st, &cap));
+    const bool exit_in_graph = d->fused && !d->nograph && cap == hipStreamCaptureStatusNone;
+    const bool entry_in_graph = exit_in_graph && d->phys_on && !d->serialized;
+    if (exit_in_graph && !d->d_xa) SML_HIP(hipMalloc(&d->d_xa, 4 * sizeof(uint64_t)));
+    const unsigned target = 4u * (d->chk_count + 1);  // the check counter once this window's check is done
+    auto exit_spec = [&](const EntrySpec *en) {  // the exit (and entry) in the window graph
+        return ExitSpec{d->d_varm,    d_fc4d, d_fc2d, run_model_exit(d, d_grid4d, d_logp, true, 0, d->d_xa),
+                        h.exit_store, en};
+    };
+    auto handed_off = [&]() {  // to the exit's in-kernel wait
+        if (!(d->chk_pending && d->chk_counted))
+            return fail(SML_ERR_STATE, "sml_dyn_run_model: the safety check did not take the counter hand-off");
+        d->chk_pending = false;
+        return (int)SML_OK;
+    };
+
+    if (entry_in_graph) {
+        if (!d->d_go) {
+            SML_HIP(hipMalloc(&d->d_go, sizeof(uint64_t)));
+            SML_HIP(hipMemset(d->d_go, 0, sizeof(uint64_t)));
+            SML_HIP(hipDeviceSynchronize());
+            d->go_count = 0;
         }
-        HopWait w = d->entry_wait;
-        w.sig = d->entry_sig;
-        d->entry_wait = HopWait{};  // one launch
-        d->entry_sig = nullptr;
-        const bool phys = d->phys_on;
-        d->sm_cur = 0;  // the window's chain starts in buffer 0
-        // the exit inside the window graph: needs the check's counter hand-off (no event
-        // wait between the window and the exit; the check below counts unless captured)
-        // and the graph path.  Its per-launch values go through d_xa
-        hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-        SML_HIP(hipStreamIsCapturing(st, &cap));
-        const bool xg = !d->nograph && cap == hipStreamCaptureStatusNone;
-        if (xg && !d->d_xa) SML_HIP(hipMalloc(&d->d_xa, 4 * sizeof(uint64_t)));
-        // and the entry inside it too (r06): specx + k_io_entry as the graph's first
-        // nodes, the safety check forked by the first row kernel's go store instead of an
-        // event after k_io_entry -- one launch boundary fewer on the chain, and the graph's
-        // launch hidden behind the entry's wait.  Not under serialised dispatch (the check,
-        // enqueued after the graph, would run after the exit that waits for it)
-        if (xg && phys && d->entry_graph && !d->serialized) {
-            if (!d->d_go) {
-                SML_HIP(hipMalloc(&d->d_go, sizeof(uint64_t)));
-                SML_HIP(hipMemset(d->d_go, 0, sizeof(uint64_t)));
-                SML_HIP(hipDeviceSynchronize());
-                d->go_count = 0;
-            }
-            const uint64_t go = ++d->go_count;
-            hipLaunchKernelGGL(k_set_xa, dim3(1), dim3(64), 0, st, d->d_xa, (uint64_t)(4u * (d->chk_count + 1)),
-                               d->exit_store_value, w.value, go);
-            SML_HIP(hipGetLastError());
-            EntrySpec en{d_grid4d, d_logp, w, d->d_go, d->d_xa + 3};
-            if (w.flag) en.w.vptr = d->d_xa + 2;
-            ExitSpec es{d->d_varm, d_fc4d, d_fc2d, IoExit{0.000001, d->d_minmax, d_grid4d, d_logp}, d->exit_store,
-                        0};
-            es.ex.cnt = d->d_chk_cnt;
-            es.ex.xa = d->d_xa;
-            es.ex.late = d->d_chk_late;
-            es.ex.timeout = d->chk_timeout;
-            es.entry = &en;
-            d->exit_store = nullptr;  // one launch
-            if (int rc = window_impl(d, nleap, delt, alph, rob, wil, stream, true, &es)) return rc;
-            // enqueued after the graph, so whatever queue it shares, its producer is ahead
-            if (int rc = launch_io_check(d, st, nullptr, go)) return rc;
-            if (!(d->chk_pending && d->chk_counted && d->mm_last == d->d_minmax))
-                return fail(SML_ERR_STATE, "sml_dyn_run_model: the safety check did not take the counter hand-off");
-            d->chk_pending = false;  // the exit waits for the check's counter itself
-            return SML_OK;
-        }
-        if (int rc = launch_entry(d, d_grid4d, d_logp, w, st, xg ? d->d_xa : nullptr,
-                                  (uint64_t)(4u * (d->chk_count + 1)), d->exit_store_value))
+        const uint64_t go = ++d->go_count;
+        hipLaunchKernelGGL(k_set_xa, dim3(1), dim3(64), 0, st, d->d_xa, (uint64_t)target, h.exit_store_value,
+                           w.value, go);
+        SML_HIP(hipGetLastError());
+        EntrySpec en{d_grid4d, d_logp, w, d->d_go, d->d_xa + 3};
+        if (w.flag) en.w.vptr = d->d_xa + 2;
+        const ExitSpec es = exit_spec(&en);
+        if (int rc = window_impl(d, nleap, delt, alph, rob, wil, st, true, &es)) return rc;
+        // enqueued after the graph, so whatever queue it shares, its producer is ahead
+        if (int rc = launch_io_check(d, st, nullptr, go)) return rc;
+        return handed_off();
+    }
+
+    if (d->fused) {  // the entry with the current impint slot's tables, as the previous window left them
+        if (int rc = launch_entry(d, d->d_tab, d_grid4d, d_logp, w, st, exit_in_graph ? d->d_xa : nullptr, target,
+                                  h.exit_store_value))
             return rc;
         if (int rc = launch_io_check(d, st, nullptr)) return rc;
-        if (xg) {
-            if (!(d->chk_pending && d->chk_counted))
-                return fail(SML_ERR_STATE, "sml_dyn_run_model: the safety check did not take the counter hand-off");
-            ExitSpec es{d->d_varm, d_fc4d, d_fc2d, IoExit{0.000001, d->mm_last, d_grid4d, d_logp}, d->exit_store,
-                        0};
-            es.ex.cnt = d->d_chk_cnt;
-            es.ex.xa = d->d_xa;
-            es.ex.late = d->d_chk_late;
-            es.ex.timeout = d->chk_timeout;
-            d->chk_pending = false;
-            d->exit_store = nullptr;  // one launch
-            return window_impl(d, nleap, delt, alph, rob, wil, stream, true, &es);
-        }
-        if (int rc = window_impl(d, nleap, delt, alph, rob, wil, stream, true)) return rc;
-    } else {
-        if (int rc = sml_dyn_from_grid(d, d_grid4d, d_logp, nullptr, stream)) return rc;
-        if (int rc = sml_dyn_window(d, nleap, delt, alph, rob, wil, stream)) return rc;
+    } else if (int rc = from_grid(d, d_grid4d, d_logp, nullptr, st, w)) {
+        return rc;
     }
-    IoExit ex{0.000001, d->mm_last, d_grid4d, d_logp};
-    if (d->chk_pending && d->chk_counted) {
-        // the exit kernel itself waits for the check's counter: no event wait (a
-        // barrier packet with a cross-queue dependency) on the window's stream.  The
-        // check is complete once the exit has run, so the next user of d_chk needs no
-        // wait either
-        ex.cnt = d->d_chk_cnt;
-        ex.target = 4u * d->chk_count;
-        ex.late = d->d_chk_late;
-        ex.timeout = d->chk_timeout;
-        d->chk_pending = false;
-    } else if (d->chk_pending) {  // the exit reads the check's min/max
-        SML_HIP(hipStreamWaitEvent(st, d->ev_chk, 0));
-        d->chk_pending = false;
+    if (exit_in_graph) {
+        if (int rc = handed_off()) return rc;
+        const ExitSpec es = exit_spec(nullptr);
+        return window_impl(d, nleap, delt, alph, rob, wil, st, true, &es);
     }
+
+    if (int rc = window_impl(d, nleap, delt, alph, rob, wil, st, d->fused)) return rc;
+    const bool counted = d->chk_pending && d->chk_counted;  // the exit waits for the counter itself,
+    if (counted) d->chk_pending = false;
+    if (int rc = wait_pending_check(d, st)) return rc;  // else its stream for the check's min/max
     if (!d->fused) {  // the fused window's last kernel did iogrid(31)'s prep + gridy already
         hipLaunchKernelGGL(k_io_prep, dim3((kMN + 127) / 128, kKX), dim3(128), 0, st, d->d_state, d->d_specin,
                            d->d_tab);
         SML_HIP(hipGetLastError());
         if (int rc = spectral_gridy(d->sp, d->d_specin, d->d_varm, kNIo, st)) return rc;
     }
-    if (int rc = spectral_gridx_run_model_exit(d->sp, d->d_varm, d_fc4d, d_fc2d, kNIoWind, ex, st)) return rc;
-    if (d->exit_store) {
-        hipLaunchKernelGGL(k_flag_store_value, dim3(1), dim3(64), 0, st, d->exit_store, d->exit_store_value);
+    if (int rc = spectral_gridx_run_model_exit(d->sp, d->d_varm, d_fc4d, d_fc2d, kNIoWind,
+                                               run_model_exit(d, d_grid4d, d_logp, counted, target, nullptr), st))
+        return rc;
+    if (h.exit_store) {
+        hipLaunchKernelGGL(k_flag_store_value, dim3(1), dim3(64), 0, st, h.exit_store, h.exit_store_value);
         SML_HIP(hipGetLastError());
-        d->exit_store = nullptr;  // one launch
     }
     return SML_OK;
 }
@@ -3252,8 +3260,8 @@ extern "C" int sml_dyn_last_safe(sml_dynamics *d, int *safe, double *minmax) {
 int sml::dyn_run_model_wait(sml_dynamics *d, const uint64_t *flag, uint64_t value, unsigned *late,
                             long long timeout) {
     SML_REQUIRE(d && flag && late, "null argument");
-    d->entry_wait = HopWait{flag, value, late};
-    d->entry_wait.timeout = timeout;
+    d->hooks.entry_wait = HopWait{flag, value, late};
+    d->hooks.entry_wait.timeout = timeout;
     return SML_OK;
 }
 
@@ -3292,7 +3300,7 @@ int sml::dyn_check_event(sml_dynamics *d, void **ev) {
 // starts: its input grid is complete and released by then
 int sml::dyn_run_model_entry_signal(sml_dynamics *d, uint64_t *counter, int *adds) {
     SML_REQUIRE(d && counter && adds, "null argument");
-    d->entry_sig = counter;
+    d->hooks.entry_sig = counter;
     *adds = spectral_specx_io_blocks();
     return SML_OK;
 }
@@ -3301,8 +3309,8 @@ int sml::dyn_run_model_entry_signal(sml_dynamics *d, uint64_t *counter, int *add
 // exit is captured there) by a one-lane store of value to *flag; flag = NULL withdraws it
 int sml::dyn_run_model_exit_store(sml_dynamics *d, uint64_t *flag, uint64_t value) {
     SML_REQUIRE(d, "null argument");
-    d->exit_store = flag;
-    d->exit_store_value = value;
+    d->hooks.exit_store = flag;
+    d->hooks.exit_store_value = value;
     return SML_OK;
 }
 

@@ -248,3 +248,105 @@ def test_run_model_with_alternating_buffers_is_bitwise_the_fixed_buffer_chain(cu
     finally:
         a.close()
         b.close()
+
+
+def _ctx(physics=True, lradsw=True, nograph=None):
+    """A context at the synthetic state; nograph: a monkeypatch that sets
+    SML_DYN_NOGRAPH=1 around the constructor only (sml_dyn_create reads it)."""
+    from speedy_ml_amd.dynamics import Dynamics
+    from speedy_ml_amd.synthetic import dyn_state, phys_boundary
+
+    if nograph is None:
+        d = Dynamics()
+    else:
+        with nograph.context() as m:
+            m.setenv("SML_DYN_NOGRAPH", "1")
+            d = Dynamics()
+    st0, forcing = dyn_state()
+    d.set_forcing(**forcing)
+    d.set_state(st0)
+    if physics:
+        d.set_physics(phys_boundary(d, forcing["phis"]))
+        d.set_rad_state(None)
+    d.set_clock(1, lradsw)
+    return d
+
+
+# nleap = 0: step(1, 2) is the window's last kernel (the one that fills the exit's
+# buffer); 4 crosses a shortwave step.  lradsw: the replay class the first window enters
+# with (from False, nleap = 4 leaves True: the second run_model enters the other class)
+@pytest.mark.parametrize("lradsw", [True, False])
+@pytest.mark.parametrize("nleap", [0, 4])
+def test_nograph_window_is_bitwise_the_graph_window(cuda, monkeypatch, nleap, lradsw):
+    """SML_DYN_NOGRAPH=1 issues the window's launches one by one instead of replaying
+    them: same kernels, same arguments, same state."""
+    a, b = _ctx(lradsw=lradsw), _ctx(lradsw=lradsw, nograph=monkeypatch)
+    try:
+        a.window(nleap)
+        b.window(nleap)
+        sa, sb = a.get_state(), b.get_state()
+        for f in sa:
+            np.testing.assert_array_equal(sa[f], sb[f], err_msg=f)
+        assert a.get_clock() == b.get_clock()
+    finally:
+        a.close()
+        b.close()
+
+
+@pytest.mark.parametrize("lradsw", [True, False])
+@pytest.mark.parametrize("nleap", [0, 4])
+def test_nograph_run_model_is_bitwise_the_graph_run_model(cuda, monkeypatch, nleap, lradsw):
+    """Two consecutive run_model calls (entry, window, exit: inside the window graph by
+    default, launched directly under SML_DYN_NOGRAPH=1) give the same forecasts and the
+    same run_speedy."""
+    import torch
+
+    g4, g2 = _grids()
+    a, b = _ctx(lradsw=lradsw), _ctx(lradsw=lradsw, nograph=monkeypatch)
+    try:
+        outs = []
+        for d in (a, b):
+            i4, i2 = _t(g4, cuda), _t(g2, cuda)
+            o4, o2 = torch.zeros_like(i4), torch.zeros_like(i2)
+            p4, p2 = torch.zeros_like(i4), torch.zeros_like(i2)
+            d.run_model(i4, i2, o4, o2, nleap=nleap)
+            s1 = d.last_safe()[0]
+            d.run_model(o4, o2, p4, p2, nleap=nleap)
+            s2 = d.last_safe()[0]
+            torch.cuda.synchronize()
+            outs.append(((s1, s2), [x.cpu().numpy() for x in (o4, o2, p4, p2)]))
+        assert outs[0][0] == outs[1][0] == (True, True)
+        for x, y in zip(outs[0][1], outs[1][1]):
+            np.testing.assert_array_equal(x, y)
+    finally:
+        a.close()
+        b.close()
+
+
+def test_run_model_without_gpu_physics_is_window_plus_q_floor(cuda):
+    """Without set_physics run_model launches its entry in front of the window graph and
+    captures only the exit in it: bitwise from_grid + window + to_grid, q floored."""
+    import torch
+
+    g4, g2 = _grids()
+    dg4, dg2 = _t(g4, cuda), _t(g2, cuda)
+    d, ref = _ctx(physics=False), _ctx(physics=False)
+    try:
+        f4, f2 = torch.zeros_like(dg4), torch.zeros_like(dg2)
+        r4, r2 = torch.zeros_like(dg4), torch.zeros_like(dg2)
+        d.run_model(dg4, dg2, f4, f2, nleap=4)
+        safe, mm = d.last_safe()
+        assert safe, mm
+        ref.from_grid(dg4, dg2)
+        ref.window(4)
+        ref.to_grid(r4, r2)
+        torch.cuda.synchronize()
+        raw = r4.cpu().numpy()
+        assert (raw[..., 3] < 1e-6).any(), "test setup: the forecast should have q below the floor somewhere"
+        want = raw.copy()
+        want[..., 3] = np.where(raw[..., 3] < 0.000001, 0.000001, raw[..., 3])
+        np.testing.assert_array_equal(f4.cpu().numpy(), want)
+        np.testing.assert_array_equal(f2.cpu().numpy(), r2.cpu().numpy())
+    finally:
+        d.close()
+        ref.close()
