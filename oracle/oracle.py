@@ -66,7 +66,7 @@ def _declare(L):
     L.orc_radius_by_region.restype = d
     L.orc_reservoir_sizes.argtypes = [i, i, i, i, vp]
     L.orc_predict.argtypes = [i, i, i, vp, vp, vp, vp, vp, i, i, d, vp, vp, vp, vp, vp, vp, i]
-    L.orc_predict_f32.argtypes = [i, i, i, vp, vp, vp, vp, vp, vp, i, i, d, vp, vp, vp, vp, vp, vp]
+    L.orc_predict_f32.argtypes = [i, i, i, vp, vp, vp, vp, vp, vp, i, i, d, vp, vp, vp, vp, vp, vp, i]
     L.orc_predict_regions.argtypes = [i, i, vp, vp, vp, vp, vp, vp, vp, vp, i, i, d, vp, vp, vp, vp, vp, vp]
     L.orc_predict_f32_regions.argtypes = [i, i, vp, vp, vp] + [vp] * 6 + [i, i, d] + [vp] * 6
     L.orc_predict_slab_ml_f32.argtypes = [i, i, vp, vp, vp, vp, vp, vp, i, d, vp, vp, vp, d, d]
@@ -250,6 +250,13 @@ def reservoir_sizes(region: int, sst: bool, numregions: int = 1152, m_nodes: int
 
 
 # ---------------------------------------------------------------- reservoir
+def _check_unstandardize(unstandardize, nout):
+    # orc_unstandardize_res walks the 2x2 region's 136 outputs: on a shorter outvec it
+    # would run past the array
+    if unstandardize and nout != 136:
+        raise ValueError(f"unstandardize=True needs the 2x2 region's 136 outputs, not {nout}")
+
+
 def predict(rows, cols, vals, win_dense, wout, feedback, local_model, x, mean, std,
             chunk_speedy=132, leakage=1.0, unstandardize=True):
     """Reference predict (mod_reservoir.f90:1416-1487).  win_dense: (ninp, n) C array
@@ -258,6 +265,7 @@ def predict(rows, cols, vals, win_dense, wout, feedback, local_model, x, mean, s
     ninp, n = win_dense.shape
     k = len(rows)
     nout = wout.shape[1]
+    _check_unstandardize(unstandardize, nout)
     rows = np.ascontiguousarray(rows, dtype=np.int32)
     cols = np.ascontiguousarray(cols, dtype=np.int32)
     vals = np.ascontiguousarray(vals, dtype=np.float64)
@@ -299,10 +307,11 @@ def predict_regions(regions, feedbacks, local_models, xs, nthreads=1, chunk_spee
 
 
 def predict_f32(rows, cols, vals_f32, win_col, win_val_f32, wout_f32, feedback, local_model, x, mean, std,
-                chunk_speedy=132, leakage=1.0):
+                chunk_speedy=132, leakage=1.0, unstandardize=True):
     """Same arithmetic with the compressed W_in (one entry per row) and fp32 weights."""
     n = len(win_col)
     nout = wout_f32.shape[1]
+    _check_unstandardize(unstandardize, nout)
     rows = np.ascontiguousarray(rows, dtype=np.int32)
     cols = np.ascontiguousarray(cols, dtype=np.int32)
     vals_f32 = np.ascontiguousarray(vals_f32, dtype=np.float32)
@@ -316,7 +325,7 @@ def predict_f32(rows, cols, vals_f32, win_col, win_val_f32, wout_f32, feedback, 
     lib().orc_predict_f32(n, len(feedback), len(rows), _p(rows), _p(cols), _p(vals_f32), _p(win_col),
                           _p(win_val_f32), _p(wout_f32), nout, chunk_speedy, leakage, _p(feedback), _p(lm),
                           _p(xx), _p(out), _p(np.ascontiguousarray(mean, dtype=np.float64)),
-                          _p(np.ascontiguousarray(std, dtype=np.float64)))
+                          _p(np.ascontiguousarray(std, dtype=np.float64)), int(bool(unstandardize)))
     return out, xx
 
 

@@ -680,11 +680,12 @@ void orc_predict_regions(int nreg, int nthreads, const int *n, const int *ninp, 
  * value per row, the structure train_reservoir writes, mod_reservoir.f90:260-278)
  * and float32 weights (the NetCDF file precision, mod_io.f90:1282); products
  * with the dense matrix's exact zeros contribute nothing, so this is the same
- * arithmetic.  Used for the CPU baseline on bounded samples. */
+ * arithmetic.  Used for the CPU baseline on bounded samples.  unstd as orc_predict's:
+ * the unstandardize is the 2x2 region's (136 outputs), so any other nout passes 0. */
 void orc_predict_f32(int n, int ninp, int k, const int *rows, const int *cols, const float *vals,
                      const int *win_col, const float *win_val, const float *wout, int nout, int chunk_speedy,
                      double leakage, const double *feedback, const double *local_model, double *x,
-                     double *outvec, const double *mean, const double *std)
+                     double *outvec, const double *mean, const double *std, int unstd)
 {
     double *y = (double *)calloc((size_t)n, sizeof(double));
     double *xa = (double *)malloc(sizeof(double) * (size_t)(n + chunk_speedy));
@@ -703,7 +704,7 @@ void orc_predict_f32(int n, int ninp, int k, const int *rows, const int *cols, c
         const float *wc = wout + (size_t)jj * nout;
         for (int o = 0; o < nout; ++o) outvec[o] = outvec[o] + (double)wc[o] * a;
     }
-    orc_unstandardize_res(outvec, 2, 2, ZGRID, mean, std, 1, 1, 33, 35);
+    if (unstd) orc_unstandardize_res(outvec, 2, 2, ZGRID, mean, std, 1, 1, 33, 35);
     free(y);
     free(xa);
 }
@@ -721,7 +722,7 @@ void orc_predict_f32_regions(int nreg, int nthreads, const int *n, const int *ni
     for (int r = 0; r < nreg; ++r)
         orc_predict_f32(n[r], ninp[r], k[r], rows[r], cols[r], vals[r], win_col[r], win_val[r], wout[r], nout,
                         chunk_speedy, leakage, feedback[r], local_model[r], x[r], outvecs + (size_t)r * nout,
-                        mean[r], std[r]);
+                        mean[r], std[r], 1);
 }
 
 /* predict_slab_ml (mod_slab_ocean_reservoir.f90:1251-1296): the slab-ocean reservoir's

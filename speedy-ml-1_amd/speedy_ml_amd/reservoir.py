@@ -136,6 +136,10 @@ class Reservoirs:
         """Cap on the v_ml readout's waves in predict_begin (0 = uncapped)."""
         check(lib().sml_res_set_read_waves(self._h, int(waves)))
 
+    def set_outvec_ld(self, ld: int):
+        """Row stride (>= nout) of the outvec arrays the context writes (sml_res_set_outvec_ld)."""
+        check(lib().sml_res_set_outvec_ld(self._h, int(ld)))
+
     def set_update_cus(self, cus: int):
         """The CUs this context's launches get (sml_res_set_update_cus; 0 = the device)."""
         check(lib().sml_res_set_update_cus(self._h, int(cus)))

@@ -100,3 +100,83 @@ def test_predict_regions_openmp_equals_predict():
     for i, (o, x) in enumerate(expect):
         np.testing.assert_array_equal(out[i], o)
         np.testing.assert_array_equal(xs[i], x)
+
+
+X_TOL = 1e-14  # the project's reservoir bounds (tests/test_reservoir_gpu.py), scaled as _check does
+OUT_TOL = 1e-11
+
+
+def _edge_weights(n, ninp, nout, ncs, seed):
+    """A reservoir of any shape: A with 6 n + n // 3 entries from per-block permutations
+    (rows of 6 or 7, as makesparse lays them), one W_in entry per row in a random column."""
+    rng = np.random.default_rng([seed, n, ninp])
+    blocks = [n] * 6 + [n // 3]
+    rows = np.concatenate([rng.permutation(n)[:b] + 1 for b in blocks]).astype(np.int32)
+    cols = np.concatenate([rng.permutation(n)[:b] + 1 for b in blocks]).astype(np.int32)
+    vals = (0.3 * rng.random(len(rows))).astype(np.float32)
+    wcol = rng.integers(0, ninp, n).astype(np.int32)
+    wval = (rng.random(n) - 0.5).astype(np.float32)
+    wval[wval == 0] = 0.25
+    wout = (0.01 * (2.0 * rng.random((ncs + n, nout)) - 1.0)).astype(np.float32)
+    x0 = rng.random(n) - 0.5
+    fb = rng.standard_normal(ninp)
+    lm = rng.standard_normal(ncs)
+    return rows, cols, vals, wcol, wval, wout, x0, fb, lm
+
+
+def _longdouble_predict(rows, cols, vals, wcol, wval, wout, x0, fb, lm, leak):
+    """predict (mod_reservoir.f90:1440-1459) in np.longdouble: the COO product with
+    duplicates adding, the one W_in entry of each row, the leaky tanh, the 1-based even
+    entries squared, W_out^T [lm; x~]."""
+    L = np.longdouble
+    x = x0.astype(L)
+    y = np.zeros(len(x0), dtype=L)
+    np.add.at(y, rows - 1, vals.astype(L) * x[cols - 1])
+    temp = wval.astype(L) * fb.astype(L)[wcol]
+    x1 = (L(1) - L(leak)) * x + L(leak) * np.tanh(y + temp)
+    xt = x1.copy()
+    xt[1::2] = x1[1::2] ** 2
+    xa = np.concatenate([lm.astype(L), xt])
+    return (wout.astype(L) * xa[:, None]).sum(axis=0), x1
+
+
+def _scaled(a, b):
+    b = np.asarray(b, dtype=np.longdouble)
+    return float((np.abs(np.asarray(a) - b) / (1.0 + np.abs(b))).max())
+
+
+def test_predict_matches_a_longdouble_restatement_off_the_usual_shapes():
+    """oracle.predict (dense W_in) and oracle.predict_f32 (compressed W_in) against the
+    longdouble restatement at leakage != 1, odd n, n of 1, across the 1024-row pass, past
+    7168 and 8192 and at the 16-bit column limit, ncs not a multiple of 4, nout not a
+    multiple of 8: the shapes tests/test_reservoir_edges_gpu.py takes the oracle as its
+    reference at."""
+    shapes = [(1, 1, 1, 0, 0.5), (63, 5, 9, 5, 0.3), (1023, 7, 24, 33, 1 / 3), (1025, 33, 136, 132, 1 / 12),
+              (7169, 1500, 4, 7, 0.25), (9001, 37, 17, 1, 0.9), (65535, 33, 9, 5, 0.3)]
+    for n, ninp, nout, ncs, leak in shapes:
+        rows, cols, vals, wcol, wval, wout, x0, fb, lm = _edge_weights(n, ninp, nout, ncs, seed=3)
+        ref_out, ref_x = _longdouble_predict(rows, cols, vals, wcol, wval, wout, x0, fb, lm, leak)
+        win = np.zeros((ninp, n))
+        win[wcol, np.arange(n)] = wval
+        mean, std = np.zeros(36), np.ones(36)
+        got = {"predict": oracle.predict(rows, cols, vals.astype(np.float64), win, wout.astype(np.float64), fb, lm,
+                                         x0, mean, std, chunk_speedy=ncs, leakage=leak, unstandardize=False),
+               "predict_f32": oracle.predict_f32(rows, cols, vals, wcol, wval, wout, fb, lm, x0, mean, std,
+                                                 chunk_speedy=ncs, leakage=leak, unstandardize=False)}
+        for name, (out, x1) in got.items():
+            ex, eo = _scaled(x1, ref_x), _scaled(out, ref_out)
+            print(f"{name} n={n} ninp={ninp} nout={nout} ncs={ncs} leak={leak:.4f}: x {ex:.2e} outvec {eo:.2e}")
+            assert ex <= X_TOL, (name, n, ex)
+            assert eo <= OUT_TOL, (name, n, eo)
+        np.testing.assert_array_equal(got["predict"][1], got["predict_f32"][1])
+        np.testing.assert_array_equal(got["predict"][0], got["predict_f32"][0])
+
+
+def test_unstandardize_refuses_other_output_counts():
+    """The unstandardize walks the 2x2 region's 136 outputs: asked for on a shorter
+    outvec it is refused instead of running past the array."""
+    import pytest
+
+    rows, cols, vals, wcol, wval, wout, x0, fb, lm = _edge_weights(63, 5, 9, 5, seed=3)
+    with pytest.raises(ValueError, match="136"):
+        oracle.predict_f32(rows, cols, vals, wcol, wval, wout, fb, lm, x0, np.zeros(36), np.ones(36), chunk_speedy=5)
