@@ -513,6 +513,9 @@ int sml_phys_sflset(const double *phi0, double *forog);
  *   fit_chunk_hybrid (src/mod_reservoir.f90:1233-1332) / fit_chunk_ml (:1175-1231):
  *                    regularisation + mldivide (src/mod_linalg.f90:109-151)
  * naug[i] = chunk_size_speedy + n (hybrid) or n (ML only); nout = 136.
+ * sml_train_create takes 2 <= nout <= 144 and naug[i] >= 2, anything else is
+ * SML_ERR_ARG: the Gram kernel loads operand rows in pairs and has no path for an
+ * operand of one row (the model's naug = chunk_size_speedy + n is never near 1).
  * Device memory: nlocal x npad^2 doubles of Gram (npad = max naug rounded up to
  * 128), so batch the regions to fit HBM (e.g. 144 regions of 6300 = 47 GB). */
 typedef struct sml_train sml_train;
@@ -522,7 +525,9 @@ int sml_train_destroy(sml_train *t);
 int sml_train_reset(sml_train *t, void *stream);
 /* one chunking_matmul batch of m time steps for every region:
  *   d_states : per region augmented_states(naug_i, m), column-major, back to back
- *   d_targets: per region targetdata(nout, m), column-major, back to back */
+ *   d_targets: per region targetdata(nout, m), column-major, back to back
+ * Stream-ordered on `stream` (blocking or not) with no host-side copy: m may change
+ * from call to call while earlier launches are still running. */
 int sml_train_accumulate(sml_train *t, const double *d_states, const double *d_targets, int m, void *stream);
 /* regularise (diag += beta_model for i < ncs, beta_res otherwise; squared and with
  * prior(i,i) = prior_val*beta_model^2 on b_trans when using_prior), solve

@@ -49,8 +49,10 @@ constexpr int kStrip = 2;   // tile rows of the T S^T strip (nout <= 256)
 constexpr int kRhs = 144;   // right-hand sides of the solves: nout = 136 rounded up to the 16-wide MFMA tile
 constexpr int kPanel = 8;   // block columns per Cholesky panel (default): trailing-update depth 1024
 
+// Set once at sml_train_create and independent of a batch's m: a launch still starting
+// workgroups while the host makes the next call reads nothing that call changes
 struct TrainRegion {
-    long long s_off, t_off;  // offsets of S (naug x m) and T (nout x m) in the batch buffers
+    long long s_pre;  // sum of the earlier regions' naug: S (naug x m) starts at s_pre * m in the batch buffer
     int naug;
     int pad_;
 };
@@ -125,7 +127,7 @@ __global__ __launch_bounds__(256, 2) void k_train_gram2(const double *__restrict
     if ((strip ? bj : bi) >= Cr) return;  // padding (bi >= bj)
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int wr = w >> 1, wc = w & 1, l16 = lane & 15, kk = lane >> 4;
-    const double *Sr = S + R.s_off, *Tr = T + R.t_off;
+    const double *Sr = S + R.s_pre * m, *Tr = T + (long long)r * nout * m;  // T is nout x m per region
     const int naug = R.naug;
     // a wave whose 64 x 64 sub-tile holds no output (rows past naug / nout, columns
     // past naug, or above the diagonal of a diagonal tile) loads its share of the LDS
@@ -973,24 +975,11 @@ struct sml_train {
     long long *d_wout_off = nullptr;
     double *d_linv = nullptr;  // L_kk^-1 per region and block column (C x 128 x 128)
     int *d_info = nullptr;
-    long long s_total = 0, t_total = 0;
-    int last_m = -1;
     // the forward substitution's stream (beside the factorisation, sml_train_solve) and
     // its fork / join events, created on the first solve
     hipStream_t fwd = nullptr;
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
 };
-
-static void set_offsets(sml_train *t, int m, std::vector<TrainRegion> &h) {
-    long long so = 0, to = 0;
-    for (int i = 0; i < t->nlocal; ++i) {
-        h[i].s_off = so;
-        h[i].t_off = to;
-        h[i].naug = t->naug[i];
-        so += (long long)t->naug[i] * m;
-        to += (long long)t->nout * m;
-    }
-}
 
 extern "C" int sml_train_destroy(sml_train *t) {
     if (!t) return SML_OK;
@@ -1006,7 +995,8 @@ extern "C" int sml_train_destroy(sml_train *t) {
 
 extern "C" int sml_train_create(int nlocal, const int *naug, int nout, sml_train **out) {
     SML_REQUIRE(out && naug && nlocal > 0, "bad argument");
-    SML_REQUIRE(nout > 0 && nout <= kRhs, "nout must be in 1..144");
+    // k_train_gram2 loads rows in pairs, clamped to (rows - 2, rows - 1): an operand of one row has no pair
+    SML_REQUIRE(nout >= 2 && nout <= kRhs, "nout must be in 2..144");
     *out = nullptr;
     sml_train *t = new (std::nothrow) sml_train();
     if (!t) return fail(SML_ERR_NOMEM, "host allocation failed");
@@ -1015,9 +1005,9 @@ extern "C" int sml_train_create(int nlocal, const int *naug, int nout, sml_train
     t->naug.assign(naug, naug + nlocal);
     int mx = 0;
     for (int i = 0; i < nlocal; ++i) {
-        if (naug[i] <= 0) {
+        if (naug[i] < 2) {
             delete t;
-            return fail(SML_ERR_ARG, "naug[%d] = %d", i, naug[i]);
+            return fail(SML_ERR_ARG, "naug[%d] = %d (must be >= 2)", i, naug[i]);
         }
         mx = naug[i] > mx ? naug[i] : mx;
     }
@@ -1035,11 +1025,17 @@ extern "C" int sml_train_create(int nlocal, const int *naug, int nout, sml_train
                     g * 8e-9);
     }
     std::vector<long long> wo(nlocal);
-    long long off = 0;
+    std::vector<TrainRegion> regs(nlocal);
+    long long off = 0, pre = 0;
     for (int i = 0; i < nlocal; ++i) {
         wo[i] = off;
         off += (long long)nout * naug[i];
+        regs[i].s_pre = pre;
+        regs[i].naug = naug[i];
+        regs[i].pad_ = 0;
+        pre += naug[i];
     }
+    SML_HIP(hipMemcpy(t->d_regs, regs.data(), nlocal * sizeof(TrainRegion), hipMemcpyHostToDevice));
     SML_HIP(hipMemcpy(t->d_wout_off, wo.data(), nlocal * sizeof(long long), hipMemcpyHostToDevice));
     static bool lds_set = false;
     if (!lds_set) {
@@ -1062,12 +1058,6 @@ extern "C" int sml_train_reset(sml_train *t, void *stream) {
 extern "C" int sml_train_accumulate(sml_train *t, const double *d_states, const double *d_targets, int m,
                                     void *stream) {
     SML_REQUIRE(t && d_states && d_targets && m > 0, "bad argument");
-    if (m != t->last_m) {
-        std::vector<TrainRegion> h(t->nlocal);
-        set_offsets(t, m, h);
-        SML_HIP(hipMemcpy(t->d_regs, h.data(), h.size() * sizeof(TrainRegion), hipMemcpyHostToDevice));
-        t->last_m = m;
-    }
     const int tiles = t->C * (t->C + 1) / 2 + kStrip * t->C;
     hipLaunchKernelGGL(k_train_gram2, dim3(tiles, t->nlocal), dim3(256), 0, (hipStream_t)stream, d_states, d_targets,
                        t->d_regs, m, t->nout, t->npad, t->d_G, t->d_B);
@@ -1079,12 +1069,6 @@ extern "C" int sml_train_solve(sml_train *t, int ncs, double beta_res, double be
                                double prior_val, double *d_wout, int *info, void *stream) {
     SML_REQUIRE(t && d_wout, "bad argument");
     SML_REQUIRE(ncs >= 0, "ncs must be >= 0");
-    if (t->last_m < 0) {  // regions table (offsets unused by the solve)
-        std::vector<TrainRegion> h(t->nlocal);
-        set_offsets(t, 1, h);
-        SML_HIP(hipMemcpy(t->d_regs, h.data(), h.size() * sizeof(TrainRegion), hipMemcpyHostToDevice));
-        t->last_m = 1;
-    }
     hipStream_t st = (hipStream_t)stream;
     const double add_model = using_prior ? beta_model * beta_model : beta_model;
     const double add_res = using_prior ? beta_res * beta_res : beta_res;
