@@ -85,6 +85,8 @@ def _declare(L):
     L.orc_sol_oz.argtypes = [d, vp, vp, vp, vp, vp]
     L.orc_sflset.argtypes = [vp, vp]
     L.orc_phypar_grid.argtypes = [vp] * 11 + [i, vp]
+    L.orc_phypar_grid_census.argtypes = [vp] * 11 + [i, vp, vp]
+    L.orc_phys_census_size.argtypes = []
     L.orc_phys_inputs.argtypes = [vp] * 12
     L.orc_train_solve.argtypes = [i, i, i, d, d, i, d, vp, vp, vp]
     L.orc_newdate.argtypes = [i, i, vp, vp]
@@ -595,14 +597,30 @@ def phys_state():
             "ssrd": np.zeros(NGP)}
 
 
-def phypar_grid(ug1, vg1, tg1, qg1, phig1, pslg1, bc, state, lradsw):
+# The branch census of orc_phys_column (the CEN_* enum of speedy_oracle_phys.c, in
+# order): what each column decided; -1 = the decision was not reached.
+CENSUS = ("cnv_psg", "cnv_ktop1", "cnv_ktop2", "cnv_lqthr", "cnv_itop", "cnv_precnv", "cnv_fqmax", "cnv_fpsa",
+          "cnv_delq", "lsc_levels", "lsc_dqmax", "cld_rhnl1", "cld_strtop", "cld_itoplt", "cld_icltop",
+          "cld_cl1cap", "cld_pr1cap", "cld_abscl2", "cld_fst", "lw_cold", "lw_hot", "lw_tshot", "sfl_tgrad",
+          "sfl_dthl", "sfl_dths", "sfl_evap1", "sfl_evap2n", "vdi_shc", "vdi_qdif", "vdi_dryadj", "qclip",
+          "cld_clccap")
+
+
+def phypar_grid(ug1, vg1, tg1, qg1, phig1, pslg1, bc, state, lradsw, census=False):
     """phypar's physics tendencies (4, kx, ngp) = u, v, t, q from grid inputs
-    (kx, ngp) / (ngp,); bc: dict of PHYS_BC arrays (ngp,); state updated in place."""
+    (kx, ngp) / (ngp,); bc: dict of PHYS_BC arrays (ngp,); state updated in place.
+    census=True: returns (tendencies, int32 (ngp, len(CENSUS)) branch census)."""
     phys_init()
     f = lambda a: np.ascontiguousarray(a, dtype=np.float64)
     bcs = np.ascontiguousarray(np.stack([np.asarray(bc[k], dtype=np.float64).ravel() for k in PHYS_BC]))
     tend = np.zeros((4, KX, NGP))
     ins = [f(x) for x in (ug1, vg1, tg1, qg1, phig1, pslg1)]
+    if census:
+        assert lib().orc_phys_census_size() == len(CENSUS)
+        cen = np.zeros((NGP, len(CENSUS)), dtype=np.int32)
+        lib().orc_phypar_grid_census(*[_p(x) for x in ins], _p(bcs), _p(state["tau2"]), _p(state["stratc"]),
+                                     _p(state["tt_rsw"]), _p(state["ssrd"]), int(bool(lradsw)), _p(tend), _p(cen))
+        return tend, cen
     lib().orc_phypar_grid(*[_p(x) for x in ins], _p(bcs), _p(state["tau2"]), _p(state["stratc"]),
                           _p(state["tt_rsw"]), _p(state["ssrd"]), int(bool(lradsw)), _p(tend))
     return tend

@@ -174,6 +174,50 @@ typedef struct {
     double *ssrd;   /* [NGP] */
 } orc_phys_state;
 
+/* Branch census: what one column decided, for the tests that must know which
+ * branches an input reaches (tests/_phys_edges.py).  One int32 per entry; -1 = the
+ * decision was not reached by this column (or this call).  Recording changes no
+ * floating-point operation: tendencies and radiation state are bitwise the same with
+ * and without it (tests/test_oracle_physics_edges.py). */
+enum {
+    CEN_CNV_PSG,     /* psg > psmin */
+    CEN_CNV_KTOP1,   /* ktop1 < nlev (-1 when psg <= psmin) */
+    CEN_CNV_KTOP2,   /* ktop2 < nlev (-1 when psg <= psmin) */
+    CEN_CNV_LQTHR,   /* convection entered by the lqthr-only branch */
+    CEN_CNV_ITOP,    /* itop after convmf (nlp = 9: none) */
+    CEN_CNV_PRECNV,  /* precnv > 0 (-1 without convection, as the next three) */
+    CEN_CNV_FQMAX,   /* fqmax cap taken */
+    CEN_CNV_FPSA,    /* fpsa ramp below 1 */
+    CEN_CNV_DELQ,    /* secondary moisture flux (delq > 0) at any level */
+    CEN_LSC_LEVELS,  /* dqa < 0: bit k for level k = 2..8 */
+    CEN_LSC_DQMAX,   /* dqmax cap taken at any condensing level (-1 without one) */
+    CEN_CLD_RHNL1,   /* rh(nl1) > rhcl1 (cloud entries: -1 when not lradsw) */
+    CEN_CLD_STRTOP,  /* cloud top before min(itop, .) (nlp = 9: none) */
+    CEN_CLD_ITOPLT,  /* itop < icltop */
+    CEN_CLD_ICLTOP,  /* final icltop (9 = none) */
+    CEN_CLD_CL1CAP,  /* cl1 capped at 1 */
+    CEN_CLD_PR1CAP,  /* pr1 capped at pmaxcl */
+    CEN_CLD_ABSCL2,  /* abscl1 * qcloud capped at abscl2 */
+    CEN_CLD_FST,     /* fst: 0 at 0, 1 in the ramp, 2 at 1 */
+    CEN_LW_COLD,     /* any level with nint(T) < 200 */
+    CEN_LW_HOT,      /* any level with nint(T) > 320 */
+    CEN_LW_TSHOT,    /* nint(surface temperature) > 320 */
+    CEN_SFL_TGRAD,   /* ta(nlev) > ta(nl1) */
+    CEN_SFL_DTHL,    /* 0 clipped at +dtheta, 1 linear positive, 2 linear negative, 3 clipped at -dtheta */
+    CEN_SFL_DTHS,    /* the same for the sea */
+    CEN_SFL_EVAP1,   /* evap1 > 0 */
+    CEN_SFL_EVAP2N,  /* sea evaporation negative (qs < q) */
+    CEN_VDI_SHC,     /* 0..3: dmse >= 0 without / with convection (+2), drh >= 0 / < 0 (+1);
+                        4: dmse < 0, drh >= drh0; 5: dmse < 0, drh < drh0 */
+    CEN_VDI_QDIF,    /* moisture diffusion: bit k for k = 3..nlev-2 */
+    CEN_VDI_DRYADJ,  /* dry adjustment: bit k for k = 1..7 */
+    CEN_QCLIP,       /* any level with q < 0 on input */
+    CEN_CLD_CLCCAP,  /* cloudc capped at 1 (-1 when not lradsw) */
+    CEN_NB
+};
+
+int orc_phys_census_size(void) { return CEN_NB; }
+
 #define LV(a, k, j) ((a)[(size_t)(k) * NGP + (j)])
 #define TAU(s, jb, k, j) ((s)->tau2[((size_t)(jb) * NLEV + (k)) * NGP + (j)])
 
@@ -182,8 +226,11 @@ typedef struct {
  * (u, v, t, q tendencies of the physics).  j = column. */
 static void orc_phys_column(int j, const double *ug1, const double *vg1, const double *tg1, const double *qg1_in,
                             const double *phig1, const double *pslg1, const orc_phys_bc *bc, orc_phys_state *st,
-                            int lradsw, double *tend)
+                            int lradsw, double *tend, int *cen)
 {
+    int cen_local[CEN_NB];
+    if (!cen) cen = cen_local;
+    for (int i = 0; i < CEN_NB; ++i) cen[i] = -1;
     const int nl1 = NLEV - 1; /* 1-based index of the level above the bottom */
     double ua[NLEV], va[NLEV], ta[NLEV], qa[NLEV], phi[NLEV], se[NLEV], rh[NLEV], qsat[NLEV];
     for (int k = 0; k < NLEV; ++k) {
@@ -196,7 +243,9 @@ static void orc_phys_column(int j, const double *ug1, const double *vg1, const d
     /* 1.2 thermodynamic variables (:73-92) */
     double psg = exp(pslg1[j]);
     double rps = 1. / psg;
+    cen[CEN_QCLIP] = 0;
     for (int k = 0; k < NLEV; ++k) {
+        if (qa[k] < 0.) cen[CEN_QCLIP] = 1;
         qa[k] = fmax(qa[k], 0.);
         se[k] = cp * ta[k] + phi[k];
     }
@@ -221,6 +270,8 @@ static void orc_phys_column(int j, const double *ug1, const double *vg1, const d
         for (int k = 2; k <= nl1; ++k) entr[k] = entr[k] * sentr;
         double rlhc = 1. / alhc, qdif = 0., msthr = 0.;
         itop = nlp;
+        cen[CEN_CNV_PSG] = psg > psmin;
+        cen[CEN_CNV_LQTHR] = 0;
         if (psg > psmin) {
             double mse0 = se[nlev - 1] + alhc * qa[nlev - 1];
             double mse1 = se[nl1 - 1] + alhc * qa[nl1 - 1];
@@ -235,6 +286,8 @@ static void orc_phys_column(int j, const double *ug1, const double *vg1, const d
                     msthr = mss2;
                 }
             }
+            cen[CEN_CNV_KTOP1] = ktop1 < nlev;
+            cen[CEN_CNV_KTOP2] = ktop2 < nlev;
             if (ktop1 < nlev) {
                 double qthr0 = rhbl * qsat[nlev - 1], qthr1 = rhbl * qsat[nl1 - 1];
                 int lqthr = (qa[nlev - 1] > qthr0 && qa[nl1 - 1] > qthr1);
@@ -242,11 +295,13 @@ static void orc_phys_column(int j, const double *ug1, const double *vg1, const d
                     itop = ktop1;
                     qdif = fmax(qa[nlev - 1] - qthr0, (mse0 - msthr) * rlhc);
                 } else if (lqthr) {
+                    cen[CEN_CNV_LQTHR] = 1;
                     itop = ktop1;
                     qdif = qa[nlev - 1] - qthr0;
                 }
             }
         }
+        cen[CEN_CNV_ITOP] = itop;
         if (itop != nlp) {
             double dfse[NLEV + 1] = {0}, dfqa[NLEV + 1] = {0};
             int k = nlev, k1 = k - 1;
@@ -257,6 +312,9 @@ static void orc_phys_column(int j, const double *ug1, const double *vg1, const d
             double fpsa = psg * fmin(1., (psg - psmin) * rdps);
             double fmass = fm0 * fpsa * fmin(fqmax, qdif / (qmax - qb));
             cbmf = fmass;
+            cen[CEN_CNV_FQMAX] = qdif / (qmax - qb) > fqmax;
+            cen[CEN_CNV_FPSA] = (psg - psmin) * rdps < 1.;
+            cen[CEN_CNV_DELQ] = 0;
             double fus = fmass * se[k - 1], fuq = fmass * qmax, fds = fmass * sb, fdq = fmass * qb;
             dfse[k] = fds - fus;
             dfqa[k] = fdq - fuq;
@@ -276,6 +334,7 @@ static void orc_phys_column(int j, const double *ug1, const double *vg1, const d
                 dfqa[k] = dfqa[k] + fdq - fuq;
                 double delq = rhil * qsat[k - 1] - qa[k - 1];
                 if (delq > 0.0) {
+                    cen[CEN_CNV_DELQ] = 1;
                     double fsq = smf * cbmf * delq;
                     dfqa[k] = dfqa[k] + fsq;
                     dfqa[nlev] = dfqa[nlev] - fsq;
@@ -284,6 +343,7 @@ static void orc_phys_column(int j, const double *ug1, const double *vg1, const d
             k = itop;
             double qsatb = qsat[k - 1] + wvi[k - 1][1] * (qsat[k] - qsat[k - 1]);
             precnv = fmax(fuq - fmass * qsatb, 0.0);
+            cen[CEN_CNV_PRECNV] = precnv > 0.0;
             dfse[k] = fus - fds + alhc * precnv;
             dfqa[k] = fuq - fdq - precnv;
             for (int kk = 1; kk <= nlev; ++kk) {
@@ -302,6 +362,7 @@ static void orc_phys_column(int j, const double *ug1, const double *vg1, const d
     {
         double qsmax = 10., rtlsc = 1. / (trlsc * 3600.), tfact = alhc / cp, prg = p0 / gg;
         double psa2 = psg * psg;
+        cen[CEN_LSC_LEVELS] = 0;
         for (int k = 2; k <= NLEV; ++k) {
             double sig2 = sig[k - 1] * sig[k - 1];
             double rhref = rhlsc + drhlsc * (sig2 - 1.);
@@ -312,6 +373,9 @@ static void orc_phys_column(int j, const double *ug1, const double *vg1, const d
                 itop = (k < itop) ? k : itop;
                 qt_lsc[k - 1] = dqa * rtlsc;
                 tt_lsc[k - 1] = tfact * fmin(-qt_lsc[k - 1], dqmax * psa2);
+                cen[CEN_LSC_LEVELS] |= 1 << k;
+                if (cen[CEN_LSC_DQMAX] < 0) cen[CEN_LSC_DQMAX] = 0;
+                if (-qt_lsc[k - 1] > dqmax * psa2) cen[CEN_LSC_DQMAX] = 1;
             } else {
                 qt_lsc[k - 1] = 0.;
                 tt_lsc[k - 1] = 0.;
@@ -352,14 +416,23 @@ static void orc_phys_column(int j, const double *ug1, const double *vg1, const d
                 icltop = k;
             }
         }
+        cen[CEN_CLD_RHNL1] = rh[nl1 - 1] > rhcl1;
+        cen[CEN_CLD_STRTOP] = icltop;
+        cen[CEN_CLD_ITOPLT] = itop < icltop;
+        cen[CEN_CLD_CL1CAP] = cloudc * rrcl > 1.;
+        cen[CEN_CLD_PR1CAP] = 86.4 * (precnv + precls) > pmaxcl;
         double cl1 = fmin(1., cloudc * rrcl);
         double pr1 = fmin(pmaxcl, 86.4 * (precnv + precls));
+        cen[CEN_CLD_CLCCAP] = wpcl * sqrt(pr1) + cl1 * cl1 > 1.;
         cloudc = fmin(1., wpcl * sqrt(pr1) + cl1 * cl1);
         icltop = (itop < icltop) ? itop : icltop;
+        cen[CEN_CLD_ICLTOP] = icltop;
         double qcloud = qa[nl1 - 1];
+        cen[CEN_CLD_ABSCL2] = abscl1 * qcloud > abscl2;
         {
             double clfact = 1.2, rgse = 1. / (gse_s1 - gse_s0);
             double fst = fmax(0., fmin(1., rgse * (gse - gse_s0)));
+            cen[CEN_CLD_FST] = (rgse * (gse - gse_s0) <= 0.) ? 0 : (rgse * (gse - gse_s0) < 1.) ? 1 : 2;
             clstr = fst * fmax(clsmax - clfact * cloudc, 0.);
             double clstrl = fmax(clstr, clsminl) * rh[NLEV - 1];
             clstr = clstr + bc->fmask1[j] * (clstrl - clstr);
@@ -446,6 +519,11 @@ static void orc_phys_column(int j, const double *ug1, const double *vg1, const d
     }
     /* 3.2 radlw(-1) (phy_radiat.f90:330-413) */
     double st4a1[NLEV], st4a2[NLEV], flux[4], dfabs[NLEV], fsfcd;
+    cen[CEN_LW_COLD] = cen[CEN_LW_HOT] = 0;
+    for (int k = 0; k < NLEV; ++k) {
+        if (lround(ta[k]) < 200) cen[CEN_LW_COLD] = 1;
+        if (lround(ta[k]) > 320) cen[CEN_LW_HOT] = 1;
+    }
     {
         for (int k = 1; k <= nl1; ++k) st4a1[k - 1] = ta[k - 1] + wvi[k - 1][1] * (ta[k] - ta[k - 1]);
         st4a2[0] = 0.75 * ta[0] + 0.25 * st4a1[0];
@@ -502,6 +580,7 @@ static void orc_phys_column(int j, const double *ug1, const double *vg1, const d
         t1[1] = t1[0] + phi0 * dt1 * rdphi0;
         t2[1] = ta[nlev - 1] + rcp * phi[nlev - 1];
         t2[0] = t2[1] - rcp * phi0;
+        cen[CEN_SFL_TGRAD] = ta[nlev - 1] > ta[nl1 - 1];
         if (ta[nlev - 1] > ta[nl1 - 1]) {
             t1[0] = ftemp0 * t1[0] + gtemp0 * t2[0];
             t1[1] = ftemp0 * t1[1] + gtemp0 * t2[1];
@@ -516,6 +595,8 @@ static void orc_phys_column(int j, const double *ug1, const double *vg1, const d
         double tskin = bc->stl_am[j] + ctday * sqclat * st->ssrd[j] * (1. - bc->alb_l[j]) * psg;
         double rdth = fstab / dtheta, astab = 0.5;
         double dthl = (tskin > t2[0]) ? fmin(dtheta, tskin - t2[0]) : fmax(-dtheta, astab * (tskin - t2[0]));
+        cen[CEN_SFL_DTHL] = (tskin > t2[0]) ? ((tskin - t2[0] > dtheta) ? 0 : 1)
+                                            : ((astab * (tskin - t2[0]) < -dtheta) ? 3 : 2);
         denvvs[1] = denvvs[0] * (1. + dthl * rdth);
         double cdldv = cdl * denvvs[0] * bc->forog[j];
         double ustr1 = -cdldv * ua[nlev - 1], vstr1 = -cdldv * va[nlev - 1];
@@ -525,6 +606,7 @@ static void orc_phys_column(int j, const double *ug1, const double *vg1, const d
         qsat0[0] = qsat_of(tskin, psg, 1.);
         double swav = bc->soilw_am[j];
         double evap1 = chl * denvvs[1] * fmax(0., swav * qsat0[0] - q1[0]);
+        cen[CEN_SFL_EVAP1] = evap1 > 0;
         double tsk3 = tskin * tskin * tskin;
         double dslr = esbc4 * tsk3;
         double slru1 = esbc * tsk3 * tskin;
@@ -547,6 +629,8 @@ static void orc_phys_column(int j, const double *ug1, const double *vg1, const d
         /* sea */
         double tsea = bc->sst_am[j];
         double dths = (tsea > t2[1]) ? fmin(dtheta, tsea - t2[1]) : fmax(-dtheta, astab * (tsea - t2[1]));
+        cen[CEN_SFL_DTHS] = (tsea > t2[1]) ? ((tsea - t2[1] > dtheta) ? 0 : 1)
+                                           : ((astab * (tsea - t2[1]) < -dtheta) ? 3 : 2);
         denvvs[2] = denvvs[0] * (1. + dths * rdth);
         q1[1] = qa[nlev - 1];
         double cdsdv = cds * denvvs[2];
@@ -555,6 +639,7 @@ static void orc_phys_column(int j, const double *ug1, const double *vg1, const d
         double shf2 = chscp * denvvs[2] * (tsea - t1[1]);
         double qs = qsat_of(tsea, psg, 1.);
         double evap2 = chs * denvvs[2] * (qs - q1[1]);
+        cen[CEN_SFL_EVAP2N] = qs < q1[1];
         double ts2 = tsea * tsea;
         double slru2 = esbc * (ts2 * ts2);
         ustr3 = ustr2 + fmask * (ustr1 - ustr2);
@@ -567,6 +652,7 @@ static void orc_phys_column(int j, const double *ug1, const double *vg1, const d
     /* 3.4 radlw(1) (phy_radiat.f90:414-458) */
     {
         double refsfc = 1. - emisfc, fsfcu = slru3, ts = tsfc;
+        cen[CEN_LW_TSHOT] = lround(ts) > 320;
         for (int jb = 0; jb < 4; ++jb) flux[jb] = fb(ts, jb) * fsfcu + refsfc * flux[jb];
         dfabs[NLEV - 1] = dfabs[NLEV - 1] + epslw * fsfcu;
         for (int jb = 0; jb < 4; ++jb)
@@ -611,6 +697,8 @@ static void orc_phys_column(int j, const double *ug1, const double *vg1, const d
         double dmse = (se[nlev - 1] - se[nl1 - 1]) + alhc * (qa[nlev - 1] - qsat[nl1 - 1]);
         double drh = rh[nlev - 1] - rh[nl1 - 1];
         double fcnv = 1.;
+        cen[CEN_VDI_SHC] = (dmse >= 0.0) ? (icnv > 0 ? 2 : 0) + (drh >= 0.0 ? 0 : 1) : (drh >= drh0 ? 4 : 5);
+        cen[CEN_VDI_QDIF] = cen[CEN_VDI_DRYADJ] = 0;
         if (dmse >= 0.0) {
             if (icnv > 0) fcnv = redshc;
             double fluxse = fcnv * fshcse * dmse;
@@ -632,6 +720,7 @@ static void orc_phys_column(int j, const double *ug1, const double *vg1, const d
                 fvdiq2 = fvdiq * sigh[k];
                 drh = rh[k] - rh[k - 1];
                 if (drh >= drh0) {
+                    cen[CEN_VDI_QDIF] |= 1 << k;
                     double fluxq = fvdiq2 * qsat[k - 1] * drh;
                     qtv[k - 1] = qtv[k - 1] + fluxq * rsig[k - 1];
                     qtv[k] = qtv[k] - fluxq * rsig[k];
@@ -640,6 +729,7 @@ static void orc_phys_column(int j, const double *ug1, const double *vg1, const d
         for (int k = 1; k <= nl1; ++k) {
             double se0 = se[k] + segrad * (phi[k - 1] - phi[k]);
             if (se[k - 1] < se0) {
+                cen[CEN_VDI_DRYADJ] |= 1 << k;
                 double fluxse = fvdise * (se0 - se[k - 1]);
                 ttv[k - 1] = ttv[k - 1] + fluxse * rsig[k - 1];
                 for (int k1 = k + 1; k1 <= nlev; ++k1) ttv[k1 - 1] = ttv[k1 - 1] - fluxse * rsig1[k - 1];
@@ -670,7 +760,20 @@ void orc_phypar_grid(const double *ug1, const double *vg1, const double *tg1, co
     const double **f = (const double **)&bc;
     for (int i = 0; i < 15; ++i) f[i] = bc_fields + (size_t)i * NGP;
     orc_phys_state st = {tau2, stratc, tt_rsw, ssrd};
-    for (int j = 0; j < NGP; ++j) orc_phys_column(j, ug1, vg1, tg1, qg1, phig1, pslg1, &bc, &st, lradsw, tend);
+    for (int j = 0; j < NGP; ++j) orc_phys_column(j, ug1, vg1, tg1, qg1, phig1, pslg1, &bc, &st, lradsw, tend, NULL);
+}
+
+/* The same with the branch census: census [NGP][orc_phys_census_size()] int32. */
+void orc_phypar_grid_census(const double *ug1, const double *vg1, const double *tg1, const double *qg1,
+                            const double *phig1, const double *pslg1, const double *bc_fields, double *tau2,
+                            double *stratc, double *tt_rsw, double *ssrd, int lradsw, double *tend, int *census)
+{
+    orc_phys_bc bc;
+    const double **f = (const double **)&bc;
+    for (int i = 0; i < 15; ++i) f[i] = bc_fields + (size_t)i * NGP;
+    orc_phys_state st = {tau2, stratc, tt_rsw, ssrd};
+    for (int j = 0; j < NGP; ++j)
+        orc_phys_column(j, ug1, vg1, tg1, qg1, phig1, pslg1, &bc, &st, lradsw, tend, census + (size_t)j * CEN_NB);
 }
 
 /* ------------------------------------------------------------ per-window forcing

@@ -26,6 +26,14 @@ def _rel(a, b):
     return np.abs(a - b).max() / max(np.abs(b).max(), 1e-300)
 
 
+def _level_rel(a, b):
+    """(kx, columns) arrays: max |a - b| / max |b| per level.  The norm over all levels
+    (_rel) lets an error in the top levels, whose tendencies are 100 to 1000 times
+    smaller than the largest, be that many times TOL."""
+    den = np.abs(b).max(axis=-1)
+    return np.abs(a - b).max(axis=-1) / np.where(den > 0, den, 1.0)
+
+
 @pytest.fixture(scope="module")
 def pg():
     import os
@@ -58,12 +66,16 @@ def test_phypar_matches_reference(dyn, pg):
         ref = pg[f"{case}_tend"]
         for v in range(4):
             assert _rel(tend[v][:, sel], ref[v]) <= TOL, (case, v, _rel(tend[v][:, sel], ref[v]))
+            lv = _level_rel(tend[v][:, sel], ref[v])
+            print(f"phypar vs reference, {case} variable {v} per level:", " ".join(f"{x:.1e}" for x in lv))
+            assert (lv <= TOL).all(), (case, v, lv)
         if case == "rad":
             rad = dyn.get_rad_state()
             np.testing.assert_allclose(rad["tau2"][..., sel], pg["rad_tau2"], rtol=1e-13, atol=0)
             np.testing.assert_allclose(rad["stratc"][:, sel], pg["rad_stratc"], rtol=1e-13, atol=0)
             np.testing.assert_allclose(rad["ssrd"][sel], pg["rad_ssrd"], rtol=1e-13, atol=1e-12)
             assert _rel(rad["tt_rsw"][:, sel], pg["rad_tt_rsw"]) <= TOL
+            assert (_level_rel(rad["tt_rsw"][:, sel], pg["rad_tt_rsw"]) <= TOL).all()
 
 
 def test_phypar_matches_oracle_on_full_grid(dyn, pg):
@@ -82,6 +94,9 @@ def test_phypar_matches_oracle_on_full_grid(dyn, pg):
         got = dyn.phypar(*ins, lradsw)
         for v in range(4):
             assert _rel(got[v], ref[v]) <= TOL, (lradsw, v, _rel(got[v], ref[v]))
+            lv = _level_rel(got[v], ref[v])
+            print(f"phypar vs oracle, lradsw {lradsw} variable {v} per level:", " ".join(f"{x:.1e}" for x in lv))
+            assert (lv <= TOL).all(), (lradsw, v, lv)
     rad = dyn.get_rad_state()
     for k in ("tau2", "stratc", "ssrd"):
         np.testing.assert_allclose(rad[k], ost[k], rtol=1e-13, atol=1e-12)
