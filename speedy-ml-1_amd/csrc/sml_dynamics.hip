@@ -617,7 +617,13 @@ __global__ void k_dyn_combine(const double *__restrict__ S, double *__restrict__
 // The CW coefficients x 8 levels of a block share sh[3][kx][CW] (LDS) for the
 // vertical couplings (dmeanc, sigdtc, geop, implic's level matrices); every sum
 // runs over k in the reference's order.  The whole block must call it (barriers).
-template <int CW, class SA, class TB>
+// KU: the caller's k is wave-uniform (a scalar: CW == 64, one level per wave).  What
+// depends on k alone is then decided by uniform branches -- the level loops end at the
+// wave's level instead of forming every level's term and selecting it away.  The
+// compiler then places a level's reads in that level's branch; pinning them in one
+// batch ahead of the branches measured no faster (profiles/spec_kernel_uniform.md).
+// Either way every value stored is formed by the same expression on the same operands.
+template <int CW, bool KU, class SA, class TB>
 __device__ inline void tail_coef(SA S, double *__restrict__ Td, double *__restrict__ phi_out,
                                  const double *__restrict__ phis, const double *__restrict__ tcorh,
                                  const double *__restrict__ qcorh, int fc, const TB &tb,
@@ -630,45 +636,76 @@ __device__ inline void tail_coef(SA S, double *__restrict__ Td, double *__restri
     sh[0][k][cc] = S(1, j4, k);
     sh[1][k][cc] = S(2, j4, k);
     __syncthreads();
+    // every level's operands of sptend (sh[0], dhs) and of geop (sh[1], xgeop1 / 2)
+    double d0[kKX], dh[kKX], t1[kKX], g1[kKX], g2[kKX];
+#pragma unroll
+    for (int kk = 0; kk < kKX; ++kk) {
+        d0[kk] = sh[0][kk][cc];
+        dh[kk] = tb.dhs(kk);
+        t1[kk] = sh[1][kk][cc];
+        g1[kk] = tb.xgeop1(kk);
+        g2[kk] = kk > 0 ? tb.xgeop2(kk) : 0.0;  // (xgeop2(1) is not used)
+    }
+    // (neighbour levels clamped and the edge cases selected: no branch around a read)
+    const int km = k > 0 ? k - 1 : 0, kp = k < kKX - 1 ? k + 1 : kKX - 1;
+    // the level's own scalars of sptend and geop
+    const double trk = tb.tref(k), trm = tb.tref(km), trp = tb.tref(kp), dhsr_k = tb.dhsr(k), tref3_k = tb.tref3(k),
+                 tref2_k = tb.tref2(k), phis_c = phis[fc], corf_k = tb.corf(k);
     double dmeanc = 0.0;
 #pragma unroll
-    for (int kk = 0; kk < kKX; ++kk) dmeanc = dmeanc + sh[0][kk][cc] * tb.dhs(kk);
+    for (int kk = 0; kk < kKX; ++kk) dmeanc = dmeanc + d0[kk] * dh[kk];
     psdt = psdt - dmeanc;
     if (m == 0 && n == 0) psdt = 0.0;  // psdt(1,1) = 0
     double sig_k = 0.0, sig_k1 = 0.0;  // sigdtc(k), sigdtc(k+1); sigdtc(1) = sigdtc(kxp) = 0
-    {
+    if constexpr (KU) {
+        // the chain ends once sigdtc(k+1) is formed (uniform): sgp, sg = the last two terms
+        double sg = 0.0, sgp = 0.0;
+#pragma unroll
+        for (int kk = 0; kk < kKX - 1; ++kk) {
+            if (kk > k) break;
+            const double nx_ = sg - dh[kk] * (d0[kk] - dmeanc);
+            sgp = sg;
+            sg = nx_;
+        }
+        if (k == kKX - 1) {  // ended at kk = k - 1; sigdtc(kxp) = 0
+            sig_k = sg;
+        } else {             // ended at kk = k (sgp = sigdtc(1) = 0 at k = 0)
+            sig_k = sgp;
+            sig_k1 = sg;
+        }
+    } else {
         double sg = 0.0;
 #pragma unroll
         for (int kk = 0; kk < kKX - 1; ++kk) {
-            const double nx_ = sg - tb.dhs(kk) * (sh[0][kk][cc] - dmeanc);
+            const double nx_ = sg - dh[kk] * (d0[kk] - dmeanc);
             if (kk == k - 1) sig_k = nx_;
             if (kk == k) sig_k1 = nx_;
             sg = nx_;
         }
     }
-    // (neighbour levels clamped and the edge cases selected: no branch around a read)
-    const int km = k > 0 ? k - 1 : 0, kp = k < kKX - 1 ? k + 1 : kKX - 1;
-    const double trk = tb.tref(k), trm = tb.tref(km), trp = tb.tref(kp);
     const double dumk_k = (k == 0) ? 0.0 : sig_k * (trk - trm);
     const double dumk_k1 = (k == kKX - 1) ? 0.0 : sig_k1 * (trp - trk);
-    tdt = tdt - (dumk_k1 + dumk_k) * tb.dhsr(k) + tb.tref3(k) * (sig_k1 + sig_k) - tb.tref2(k) * dmeanc;
+    tdt = tdt - (dumk_k1 + dumk_k) * dhsr_k + tref3_k * (sig_k1 + sig_k) - tref2_k * dmeanc;
     // geop(j4)  (dyn_geop.f90:16-32)
     // (every level's term formed, the ones below k selected away: the sum and its
     // order are the reference's, and the LDS reads issue together instead of one
-    // dependent round trip per level of a runtime-bounded loop)
-    double phi = phis[fc] + tb.xgeop1(kKX - 1) * sh[1][kKX - 1][cc];
+    // dependent round trip per level of a runtime-bounded loop.  KU: the sum stops at
+    // the wave's level by a uniform branch, its operands read above)
+    double phi = phis_c + g1[kKX - 1] * t1[kKX - 1];
 #pragma unroll
     for (int kk = kKX - 2; kk >= 0; --kk) {
-        const double nx = phi + tb.xgeop2(kk + 1) * sh[1][kk + 1][cc] + tb.xgeop1(kk) * sh[1][kk][cc];
+        if constexpr (KU)
+            if (kk < k) break;  // (uniform)
+        const double nx = phi + g2[kk + 1] * t1[kk + 1] + g1[kk] * t1[kk];
         phi = kk >= k ? nx : phi;
     }
     {
-        const double pc = phi + tb.corf(k) * (sh[1][kp][cc] - sh[1][km][cc]);
+        const double pc = phi + corf_k * (sh[1][kp][cc] - sh[1][km][cc]);
         if (m == 0 && k >= 1 && k <= kKX - 2) phi = pc;
     }
     if (phi_out) phi_out[(size_t)k * kSF + c] = phi;
     {
-        const double d1 = phi + kRgas * tb.tref(k) * S(4, j4, 0);
+        const double d1 = phi + kRgas * trk * S(4, j4, 0);
         const double lapd = -(d1 * tb.el2_n(n));
         divdt = divdt - lapd;
     }
@@ -748,17 +785,6 @@ __device__ inline void tail_coef(SA S, double *__restrict__ Td, double *__restri
     timint(3, k, trdt);
 }
 
-// the barriers tail_coef executes, for threads of a block that hold no coefficient
-// (keep in step with tail_coef: 1 in sptend, 3 in implic when alph != 0)
-__device__ inline void tail_coef_barriers(double alph) {
-    __syncthreads();
-    if (alph != 0.0) {
-        __syncthreads();
-        __syncthreads();
-        __syncthreads();
-    }
-}
-
 // tail kernel of the unfused step: a block owns 32 real coefficients x 8 levels
 constexpr int kTailC = 32;
 __global__ __launch_bounds__(256) void k_dyn_tail(double *__restrict__ st, double *__restrict__ Td,
@@ -775,9 +801,11 @@ __global__ __launch_bounds__(256) void k_dyn_tail(double *__restrict__ st, doubl
         const size_t off = var == 0 ? kOffVor : var == 1 ? kOffDiv : var == 2 ? kOffT : kOffTr;
         return st[off + ((size_t)(lev - 1) * kKX + kk) * kSF + c];
     };
-    tail_coef<kTailC>(S, Td, phi_out, phis, tcorh, qcorh, c, GTab{T, m}, sh, cc, k, c, m, n, Td[kTVor + (size_t)k * kSF + c],
-                      Td[kTDiv + (size_t)k * kSF + c], Td[kTT + (size_t)k * kSF + c], Td[kTTr + (size_t)k * kSF + c],
-                      Td[kTPs + c], j1, j4, dt, alph, rob, wil);
+    // (a wave spans two levels at kTailC = 32: k is per lane, the branch-free form)
+    tail_coef<kTailC, false>(S, Td, phi_out, phis, tcorh, qcorh, c, GTab{T, m}, sh, cc, k, c, m, n,
+                             Td[kTVor + (size_t)k * kSF + c], Td[kTDiv + (size_t)k * kSF + c],
+                             Td[kTT + (size_t)k * kSF + c], Td[kTTr + (size_t)k * kSF + c], Td[kTPs + c], j1, j4, dt,
+                             alph, rob, wil);
 }
 
 // ======================================================= fused step
@@ -813,6 +841,13 @@ __device__ __attribute__((always_inline)) inline void store2(double *base, size_
 }
 
 constexpr int kCW = 2 * kNX;                  // real coefficients (n, p) of one m
+// The per-m kernels run one thread per (coefficient cc, level k), k = threadIdx.x / kCW.
+// kCW is the wavefront size, so a wave holds one level and k is the wave's index: read
+// through readfirstlane it is a scalar to the compiler, and everything that depends on
+// the level alone (edge levels, the level sums' bounds, table and state rows) is decided
+// once per wave on the scalar unit instead of per lane with compares and selects.
+static_assert(kCW == 64, "one level per 64-lane wave: wave_index() is the level index of the per-m kernels");
+__device__ inline int wave_index() { return __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)); }
 // iogrid's field-major work layout, both directions: [u 8 | v 8 | t 8 | q 8 | ps]
 constexpr int kNIo = 4 * kKX + 1;
 constexpr int kNIoWind = 2 * kKX;
@@ -896,7 +931,9 @@ __device__ inline void inv_inputs(const double *Sst, double *In, const double *p
     // one thread per (coefficient cc = 2 n + p, level k) (512 threads): the fields of
     // level k, in the same expressions as k_dyn_prep
     const bool phys = nin > kNInv;
-    const int cc = threadIdx.x & (kCW - 1), k = threadIdx.x / kCW, n = cc >> 1, p = cc & 1;
+    // (k wave-uniform, wave_index(): the k == 0 fields, the m == 0 correction and geop's
+    // bound below are uniform branches)
+    const int cc = threadIdx.x & (kCW - 1), k = wave_index(), n = cc >> 1, p = cc & 1;
     auto sv = [&](int var, int lev, int kk, int c2) { return Sst[smi(var, lev, kk, c2)]; };
     auto put = [&](int f, double v) { In[f * kCW + cc] = v; };
 #pragma unroll
@@ -922,11 +959,23 @@ __device__ inline void inv_inputs(const double *Sst, double *In, const double *p
     // phypar's level-1 inputs: t1, q1, geop(1) (geop_at), ps1, ucos1, vcos1
     put(kPT1 + k, sv(2, 1, k, cc));
     put(kPQ1 + k, sv(3, 1, k, cc));
-    double phi = phis_m[cc] + tb.xgeop1(kKX - 1) * sv(2, 1, kKX - 1, cc);
+    // (the sum ends at the wave's level by a uniform branch.  The operands are not pinned
+    // in one batch ahead of the branches: the compiler's own placement, each level's
+    // reads in its branch, measured faster -- the phase 1.12-1.16 us against 1.28-1.32
+    // pinned and 1.24 branch-free, profiles/spec_kernel_uniform.md)
+    double t1[kKX], g1[kKX], g2[kKX];
 #pragma unroll
-    for (int kk = kKX - 2; kk >= 0; --kk) {  // levels below k selected away (as in tail_coef)
-        const double nx = phi + tb.xgeop2(kk + 1) * sv(2, 1, kk + 1, cc) + tb.xgeop1(kk) * sv(2, 1, kk, cc);
-        phi = kk >= k ? nx : phi;
+    for (int kk = 0; kk < kKX; ++kk) {
+        t1[kk] = sv(2, 1, kk, cc);
+        g1[kk] = tb.xgeop1(kk);
+        g2[kk] = kk > 0 ? tb.xgeop2(kk) : 0.0;  // (xgeop2(1) is not used)
+    }
+    double phi = phis_m[cc] + g1[kKX - 1] * t1[kKX - 1];
+#pragma unroll
+    for (int kk = kKX - 2; kk >= 0; --kk) {
+        if (kk < k) break;  // (uniform)
+        const double nx = phi + g2[kk + 1] * t1[kk + 1] + g1[kk] * t1[kk];
+        phi = nx;
     }
     {
         const int km = k > 0 ? k - 1 : 0, kp = k < kKX - 1 ? k + 1 : kKX - 1;
@@ -976,7 +1025,7 @@ __device__ inline GridyB gridy_operands(const double *__restrict__ pinv, int m) 
 
 __device__ inline void gridy_m(const double *In, const GridyB &gb, double *__restrict__ varm, int m, int nf,
                                int tile0 = 0, int tile1 = -1) {
-    const int wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
+    const int wave = wave_index(), nw = blockDim.x >> 6;
     const int l = threadIdx.x & 63, r = l & 15, kk = l >> 4;
     const int tend = tile1 < 0 ? (nf + 7) / 8 : tile1;
     // work unit u = (tile, latitude half): half 0 the rows j < 16 (b00 / b10), half 1
@@ -993,6 +1042,10 @@ __device__ inline void gridy_m(const double *In, const GridyB &gb, double *__res
         for (int s = 0; s < 4; ++s) {
             const int n_odd = 2 * (4 * s + kk);  // n = 1,3,.. (1-based): symmetric part
             const int n_even = n_odd + 1;        // n = 2,4,..: antisymmetric part
+            // (the product does not need the zeroing -- a lane past the last field holds
+            // its own column r of the B operand and skips its stores -- but without it
+            // the compiler pairs and batches these reads and the phase measured 2.00
+            // against 1.68 us: kept, profiles/spec_kernel_uniform.md)
             const double a0 = ok ? a[2 * n_odd] : 0.0;
             const double a1 = ok ? a[2 * n_even] : 0.0;
             // the transposed product (Legendre operand first: the same products summed
@@ -1020,7 +1073,7 @@ __device__ inline void gridy_m(const double *In, const GridyB &gb, double *__res
 // stores): iogrid(31)'s inverse Legendre of the io fields, fused into the window's
 // last per-m kernel (run_model)
 __device__ inline void gridy_io(const double *In, const GridyB &gb, double *__restrict__ varm, int m, int nf) {
-    const int wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
+    const int wave = wave_index(), nw = blockDim.x >> 6;
     const int l = threadIdx.x & 63, r = l & 15, kk = l >> 4;
     for (int tile = wave; tile < (nf + 7) / 8; tile += nw) {
         const int f0 = tile * 8;
@@ -1032,6 +1085,7 @@ __device__ inline void gridy_io(const double *In, const GridyB &gb, double *__re
         for (int s = 0; s < 4; ++s) {
             const int n_odd = 2 * (4 * s + kk);
             const int n_even = n_odd + 1;
+            // (the zeroing kept as in gridy_m, where dropping it measured slower)
             const double a0 = ok ? a[2 * n_odd] : 0.0;
             const double a1 = ok ? a[2 * n_even] : 0.0;
             acc00 = MFMA64(a0, gb.b00[s], acc00);
@@ -1538,7 +1592,7 @@ __global__ __launch_bounds__(kSpecBlk) void k_st_spec(
     if (m >= kMX) return;  // (block-uniform: the grid's idle blocks)
     const bool lead = half == 0;
     if (!lead) dbg = nullptr;
-    const int wave = threadIdx.x >> 6, l = threadIdx.x & 63, r = l & 15, kk = l >> 4;
+    const int wave = wave_index(), l = threadIdx.x & 63, r = l & 15, kk = l >> 4;
     const int sk = next_j2 > 0 ? 1 : 3;
     stamp(dbg, sk, 0);
     // a) specy (k_specy's tiling: 8 fields x Re/Im per wave), the wave's A operands
@@ -1623,15 +1677,15 @@ __global__ __launch_bounds__(kSpecBlk) void k_st_spec(
     stamp(dbg, sk, 1);
     auto tile_mma = [&](int tile, const double (&vn)[kIY / 4], const double (&vs)[kIY / 4]) {
         const int f0 = tile * 8;
-        const bool ok = f0 + (r >> 1) < kNFwd;
+        // the lanes of fields >= kNFwd (the last tile's) loaded field 0 (tile_load: in
+        // bounds, finite) and their operands are not zeroed: they are rows of the MFMA's A
+        // operand, output row i depends on A's row i alone, and those rows are skipped at
+        // the stores below -- they can reach no stored value
         d4 accS = {0, 0, 0, 0}, accD = accS;
 #pragma unroll
         for (int s = 0; s < kIY / 4; ++s) {
-            double aS = 0.0, aD = 0.0;
-            if (ok) {
-                aS = (vn[s] + vs[s]) * wv[s];
-                aD = (vn[s] - vs[s]) * wv[s];
-            }
+            const double aS = (vn[s] + vs[s]) * wv[s];
+            const double aD = (vn[s] - vs[s]) * wv[s];
             accS = MFMA64(aS, bS[s], accS);
             accD = MFMA64(aD, bD[s], accD);
         }
@@ -1670,9 +1724,10 @@ __global__ __launch_bounds__(kSpecBlk) void k_st_spec(
     __syncthreads();  // S, Sst, Fm, the tables complete
     const LTab tb{tm};
     stamp(dbg, sk, 2);
-    // b) combine (k_dyn_combine) for coefficient (n, p) at level k: threads 0..511
-    const bool holds = threadIdx.x < kSpecThreads;
-    const int cc = threadIdx.x & (kCW - 1), k = holds ? threadIdx.x / kCW : 0;
+    // b) combine (k_dyn_combine) for coefficient (n, p) at level k: every thread of the
+    // block holds one, k the wave's index (wave-uniform)
+    static_assert(kSpecBlk == kSpecThreads, "k_st_spec: one thread per (coefficient, level), none idle in the tail");
+    const int cc = threadIdx.x & (kCW - 1), k = wave;
     const int n = cc >> 1, p = cc & 1;
     const int c = ci(p, m, n);
     auto fl = [&](int f) { return [=](int pp, int nn) { return S[f * kCW + 2 * nn + pp]; }; };
@@ -1689,18 +1744,15 @@ __global__ __launch_bounds__(kSpecBlk) void k_st_spec(
     }
     // c) sptend / implic / diffusion / time integration on the LDS state
     auto SA = [&](int var, int lev, int kk2) -> double & { return Sst[smi(var, lev, kk2, cc)]; };
-    if (holds)
-        tail_coef<kCW>(SA, lead ? Td : nullptr, lead && next_j2 <= 0 ? phi_out : nullptr, Fm, Fm + kCW, Fm + 2 * kCW, cc, tb, sh, cc, k, c, m, n, vo, dv - lapv, tdt0,
-                       trdt0, psdt, j1, j4, dt, alph, rob, wil);
-    else
-        tail_coef_barriers(alph);
+    tail_coef<kCW, true>(SA, lead ? Td : nullptr, lead && next_j2 <= 0 ? phi_out : nullptr, Fm, Fm + kCW, Fm + 2 * kCW,
+                         cc, tb, sh, cc, k, c, m, n, vo, dv - lapv, tdt0, trdt0, psdt, j1, j4, dt, alph, rob, wil);
     __syncthreads();  // S is free, Sst complete
     stamp(dbg, sk, 4);
     if (next_j2 <= 0) {  // the run of fused steps ends: the state straight into the reference layout
         if (!lead) return;  // block-uniform
         for (int i = threadIdx.x; i < kSM; i += kSpecBlk) put_state(state_out, m, i, Sst[i]);
         if (io_varm) {  // run_model: iogrid(31)'s k_io_prep + gridy of this m (block-uniform)
-            if (holds) io_prep_m(Sst, tb, k, cc, [&](int f, double v) { S[f * kCW + cc] = v; });
+            io_prep_m(Sst, tb, k, cc, [&](int f, double v) { S[f * kCW + cc] = v; });
             __syncthreads();
             gridy_io(S, gridy_operands_slice(V + kVPinv), io_varm, m, kNIo);
         }
@@ -1717,7 +1769,7 @@ __global__ __launch_bounds__(kSpecBlk) void k_st_spec(
             store2(sm_out, (size_t)m * kSM + 2 * ((size_t)q * kSpecBlk + threadIdx.x), v[q].x, v[q].y);
     }
     // d) the next step's inverse-transform inputs (k_dyn_prep) and gridy
-    if (holds) inv_inputs(Sst, S, Fm, tb, m, next_j2, n1, nin);
+    inv_inputs(Sst, S, Fm, tb, m, next_j2, n1, nin);
     __syncthreads();
     stamp(dbg, sk, 5);
     {
@@ -1804,7 +1856,8 @@ __global__ __launch_bounds__(kSpecThreads) void k_io_entry(const double *__restr
     constexpr int RT = (kTabMDoubles / 2 + kSpecThreads - 1) / kSpecThreads;
     __shared__ double V[2 * RT * kSpecThreads];  // this m's tables (TabM), staged as k_st_spec does
     const int m = blockIdx.x, tid = threadIdx.x;
-    const int wave = tid >> 6, l = tid & 63, r = l & 15, kk = l >> 4;
+    // (wave: also the level k of the thread's coefficient, wave-uniform)
+    const int wave = wave_index(), l = tid & 63, r = l & 15, kk = l >> 4;
     // every global load of the entry is issued before the first wait (one memory round
     // trip): level 2 of the slice (k_state_to_m), phis(m), specy's operands and
     // gridy's Legendre columns.  Element i = tid + 512 q of the slice has lev = q % 2,
@@ -1814,7 +1867,7 @@ __global__ __launch_bounds__(kSpecThreads) void k_io_entry(const double *__restr
     double s2[kSI / 2];
 #pragma unroll
     for (int q = 1; q < kSI; q += 2) {  // level 2 (lev index 1); level 1 comes from the combine
-        const int cc = tid % kCW, k = tid / kCW, var = q / 2;
+        const int cc = tid % kCW, k = wave, var = q / 2;
         const int c = ci(cc & 1, m, cc >> 1);
         double v = 0.0;
         if (var < 4) {
@@ -1865,11 +1918,10 @@ __global__ __launch_bounds__(kSpecThreads) void k_io_entry(const double *__restr
         d4 accS = {0, 0, 0, 0}, accD = accS;
 #pragma unroll
         for (int s = 0; s < kIY / 4; ++s) {
-            double aS = 0.0, aD = 0.0;
-            if (ok) {
-                aS = (vn[s] + vs[s]) * wv[s];
-                aD = (vn[s] - vs[s]) * wv[s];
-            }
+            // (fields >= kNIo: field 0's values, not zeroed -- rows of the A operand whose
+            // output rows are skipped at the stores below, as in k_st_spec's specy)
+            const double aS = (vn[s] + vs[s]) * wv[s];
+            const double aD = (vn[s] - vs[s]) * wv[s];
             accS = MFMA64(aS, bS[s], accS);
             accD = MFMA64(aD, bD[s], accD);
         }
@@ -1885,7 +1937,7 @@ __global__ __launch_bounds__(kSpecThreads) void k_io_entry(const double *__restr
     __syncthreads();
     // b) k_io_combine: vdspec's vds + spec, trunct, into level 1 (ppo_iogrid.f90:524-538)
     const LTab tb{reinterpret_cast<const TabM *>(V)};
-    const int cc = tid & (kCW - 1), k = tid / kCW, n = cc >> 1, p = cc & 1, c = ci(p, m, n);
+    const int cc = tid & (kCW - 1), k = wave, n = cc >> 1, p = cc & 1, c = ci(p, m, n);
     {
         auto fl = [&](int f) { return [=](int pp, int nn) { return S[f * kCW + 2 * nn + pp]; }; };
         const double trf = tb.trfilt_n(n);
