@@ -623,39 +623,43 @@ __global__ void k_dyn_combine(const double *__restrict__ S, double *__restrict__
 // compiler then places a level's reads in that level's branch; pinning them in one
 // batch ahead of the branches measured no faster (profiles/spec_kernel_uniform.md).
 // Either way every value stored is formed by the same expression on the same operands.
-template <int CW, bool KU, class SA, class TB>
-__device__ inline void tail_coef(SA S, double *__restrict__ Td, double *__restrict__ phi_out,
-                                 const double *__restrict__ phis, const double *__restrict__ tcorh,
-                                 const double *__restrict__ qcorh, int fc, const TB &tb,
-                                 double (*sh)[kKX][CW], int cc, int k, int c, int m, int n, double vordt, double divdt,
-                                 double tdt, double trdt, double psdt, int j1, int j4, double dt, double alph,
-                                 double rob, double wil) {
-    // S(var, lev, kk): the state of coefficient c (var 0..4 = vor, div, t, tr, ps at
-    // kk = 0; lev 1 or 2), updated in place; phis / tcorh / qcorh at index fc
+//
+// The tail comes in two halves.  tail_pre is the stage that reads the state and the
+// tables only -- sptend's dmeanc and sigdtc chain, geop's phi with lapd, hordif's
+// corrected t and tr -- and none of grtend's tendencies: k_st_spec runs it while specy's
+// Fourier operands are still in flight.  tail_post is everything from
+// psdt = psdt - dmeanc on and holds all of implic's barriers.  Only values that were
+// separate values in the one-piece form cross from one half to the other, so
+// -ffp-contract=on contracts the same products into the same FMAs.
+struct TailPre {
+    double dmeanc, sig_k, sig_k1, dumk_k, dumk_k1, lapd, ctmp, cq;
+};
+
+// L(v, kk): every level's div (v = 0) and t (v = 1) at time level j4 of this coefficient,
+// as the other levels' threads hold them (the caller has made them visible)
+template <bool KU, class SA, class LV, class TB>
+__device__ inline TailPre tail_pre(SA S, LV L, double *__restrict__ phi_out, const double *__restrict__ phis,
+                                   const double *__restrict__ tcorh, const double *__restrict__ qcorh, int fc,
+                                   const TB &tb, int k, int c, int m, int n, int j4) {
+    TailPre r;
     // ---- sptend(divdt, tdt, psdt, j4)  (dyn_sptend.f90:29-66)
-    sh[0][k][cc] = S(1, j4, k);
-    sh[1][k][cc] = S(2, j4, k);
-    __syncthreads();
-    // every level's operands of sptend (sh[0], dhs) and of geop (sh[1], xgeop1 / 2)
+    // every level's operands of sptend (div, dhs) and of geop (t, xgeop1 / 2)
     double d0[kKX], dh[kKX], t1[kKX], g1[kKX], g2[kKX];
 #pragma unroll
     for (int kk = 0; kk < kKX; ++kk) {
-        d0[kk] = sh[0][kk][cc];
+        d0[kk] = L(0, kk);
         dh[kk] = tb.dhs(kk);
-        t1[kk] = sh[1][kk][cc];
+        t1[kk] = L(1, kk);
         g1[kk] = tb.xgeop1(kk);
         g2[kk] = kk > 0 ? tb.xgeop2(kk) : 0.0;  // (xgeop2(1) is not used)
     }
     // (neighbour levels clamped and the edge cases selected: no branch around a read)
     const int km = k > 0 ? k - 1 : 0, kp = k < kKX - 1 ? k + 1 : kKX - 1;
     // the level's own scalars of sptend and geop
-    const double trk = tb.tref(k), trm = tb.tref(km), trp = tb.tref(kp), dhsr_k = tb.dhsr(k), tref3_k = tb.tref3(k),
-                 tref2_k = tb.tref2(k), phis_c = phis[fc], corf_k = tb.corf(k);
+    const double trk = tb.tref(k), trm = tb.tref(km), trp = tb.tref(kp), phis_c = phis[fc], corf_k = tb.corf(k);
     double dmeanc = 0.0;
 #pragma unroll
     for (int kk = 0; kk < kKX; ++kk) dmeanc = dmeanc + d0[kk] * dh[kk];
-    psdt = psdt - dmeanc;
-    if (m == 0 && n == 0) psdt = 0.0;  // psdt(1,1) = 0
     double sig_k = 0.0, sig_k1 = 0.0;  // sigdtc(k), sigdtc(k+1); sigdtc(1) = sigdtc(kxp) = 0
     if constexpr (KU) {
         // the chain ends once sigdtc(k+1) is formed (uniform): sgp, sg = the last two terms
@@ -683,9 +687,11 @@ __device__ inline void tail_coef(SA S, double *__restrict__ Td, double *__restri
             sg = nx_;
         }
     }
-    const double dumk_k = (k == 0) ? 0.0 : sig_k * (trk - trm);
-    const double dumk_k1 = (k == kKX - 1) ? 0.0 : sig_k1 * (trp - trk);
-    tdt = tdt - (dumk_k1 + dumk_k) * dhsr_k + tref3_k * (sig_k1 + sig_k) - tref2_k * dmeanc;
+    r.dmeanc = dmeanc;
+    r.sig_k = sig_k;
+    r.sig_k1 = sig_k1;
+    r.dumk_k = (k == 0) ? 0.0 : sig_k * (trk - trm);
+    r.dumk_k1 = (k == kKX - 1) ? 0.0 : sig_k1 * (trp - trk);
     // geop(j4)  (dyn_geop.f90:16-32)
     // (every level's term formed, the ones below k selected away: the sum and its
     // order are the reference's, and the LDS reads issue together instead of one
@@ -700,15 +706,32 @@ __device__ inline void tail_coef(SA S, double *__restrict__ Td, double *__restri
         phi = kk >= k ? nx : phi;
     }
     {
-        const double pc = phi + corf_k * (sh[1][kp][cc] - sh[1][km][cc]);
+        const double pc = phi + corf_k * (L(1, kp) - L(1, km));
         if (m == 0 && k >= 1 && k <= kKX - 2) phi = pc;
     }
     if (phi_out) phi_out[(size_t)k * kSF + c] = phi;
     {
         const double d1 = phi + kRgas * trk * S(4, j4, 0);
-        const double lapd = -(d1 * tb.el2_n(n));
-        divdt = divdt - lapd;
+        r.lapd = -(d1 * tb.el2_n(n));
     }
+    // hordif's corrected temperature and tracer (dyn_step.f90:60-112)
+    r.ctmp = S(2, 1, k) + tcorh[fc] * tb.tcorv(k);
+    r.cq = S(3, 1, k) + qcorh[fc] * tb.qcorv(k);
+    return r;
+}
+
+template <int CW, class SA, class TB>
+__device__ inline void tail_post(SA S, const TailPre &pre, double *__restrict__ Td, const TB &tb,
+                                 double (*sh)[kKX][CW], int cc, int k, int c, int m, int n, double vordt, double divdt,
+                                 double tdt, double trdt, double psdt, int j1, double dt, double alph, double rob,
+                                 double wil) {
+    const double dmeanc = pre.dmeanc, sig_k = pre.sig_k, sig_k1 = pre.sig_k1, dumk_k = pre.dumk_k,
+                 dumk_k1 = pre.dumk_k1, ctmp = pre.ctmp;
+    const double dhsr_k = tb.dhsr(k), tref3_k = tb.tref3(k), tref2_k = tb.tref2(k);
+    psdt = psdt - dmeanc;
+    if (m == 0 && n == 0) psdt = 0.0;  // psdt(1,1) = 0
+    tdt = tdt - (dumk_k1 + dumk_k) * dhsr_k + tref3_k * (sig_k1 + sig_k) - tref2_k * dmeanc;
+    divdt = divdt - pre.lapd;
     // ---- implic(divdt, tdt, psdt)  (dyn_implic.f90:22-67)
     if (alph != 0.0) {
         // tdt into the third plane: sptend's reads of sh[0] need no barrier of their
@@ -738,7 +761,6 @@ __device__ inline void tail_coef(SA S, double *__restrict__ Td, double *__restri
     const double dmp = tb.dmp_n(n), dmp1 = tb.dmp1_n(n), dmpd = tb.dmpd_n(n), dmp1d = tb.dmp1d_n(n);
     vordt = (vordt - dmp * S(0, 1, k)) * dmp1;
     divdt = (divdt - dmpd * S(1, 1, k)) * dmp1d;
-    const double ctmp = S(2, 1, k) + tcorh[fc] * tb.tcorv(k);
     tdt = (tdt - dmp * ctmp) * dmp1;
     if (k == 0) {
         if (m == 0) {  // stratospheric drag on the zonal mean, top level (:78-82)
@@ -751,10 +773,7 @@ __device__ inline void tail_coef(SA S, double *__restrict__ Td, double *__restri
         divdt = (divdt - dmps * S(1, 1, 0)) * dmp1s;
         tdt = (tdt - dmps * ctmp) * dmp1s;
     }
-    {
-        const double cq = S(3, 1, k) + qcorh[fc] * tb.qcorv(k);
-        trdt = (trdt - dmpd * cq) * dmp1d;
-    }
+    trdt = (trdt - dmpd * pre.cq) * dmp1d;
     if (dt <= 0.0) {  // tendencies only (dyn_step.f90:109)
         if (!Td) return;
         Td[kTVor + (size_t)k * kSF + c] = vordt;
@@ -783,6 +802,25 @@ __device__ inline void tail_coef(SA S, double *__restrict__ Td, double *__restri
     timint(1, k, divdt);
     timint(2, k, tdt);
     timint(3, k, trdt);
+}
+
+// the whole tail (k_dyn_tail): the levels' div and t of time level j4 meet in sh[0] /
+// sh[1], then tail_pre and tail_post
+template <int CW, bool KU, class SA, class TB>
+__device__ inline void tail_coef(SA S, double *__restrict__ Td, double *__restrict__ phi_out,
+                                 const double *__restrict__ phis, const double *__restrict__ tcorh,
+                                 const double *__restrict__ qcorh, int fc, const TB &tb,
+                                 double (*sh)[kKX][CW], int cc, int k, int c, int m, int n, double vordt, double divdt,
+                                 double tdt, double trdt, double psdt, int j1, int j4, double dt, double alph,
+                                 double rob, double wil) {
+    // S(var, lev, kk): the state of coefficient c (var 0..4 = vor, div, t, tr, ps at
+    // kk = 0; lev 1 or 2), updated in place; phis / tcorh / qcorh at index fc
+    sh[0][k][cc] = S(1, j4, k);
+    sh[1][k][cc] = S(2, j4, k);
+    __syncthreads();
+    const TailPre pre = tail_pre<KU>(S, [&](int v, int kk) { return sh[v][kk][cc]; }, phi_out, phis, tcorh, qcorh, fc,
+                                     tb, k, c, m, n, j4);
+    tail_post<CW>(S, pre, Td, tb, sh, cc, k, c, m, n, vordt, divdt, tdt, trdt, psdt, j1, dt, alph, rob, wil);
 }
 
 // tail kernel of the unfused step: a block owns 32 real coefficients x 8 levels
@@ -816,7 +854,8 @@ __global__ __launch_bounds__(256) void k_dyn_tail(double *__restrict__ st, doubl
 //   k_st_gridspec_p (with GPU physics): gridx, the grid-point dynamics beside phypar
 //               (its roles on waves of their own), specx, in one launch per row
 //   k_st_spec   (zonal wavenumber m, 512 threads = 64 coefficients x 8 levels):
-//               specy -> combine (vds, lap) -> sptend / geop / implic / hordif /
+//               the tail's state-only half (tail_pre: sptend's and geop's level
+//               chains) -> specy -> combine (vds, lap) -> sptend / implic / hordif /
 //               timint -> the NEXT step's inverse-transform inputs from the new
 //               state (uvspec, grad, geop) -> gridy
 //   k_st_inv    (m): the inverse-transform inputs + gridy from the state in memory,
@@ -1155,9 +1194,6 @@ constexpr int kSpecSplit = 2;             // k_st_spec blocks per m (the next st
 // placement gives the same results.
 #ifndef SML_SPEC_STRIDE
 #define SML_SPEC_STRIDE 32
-#endif
-#ifndef SML_SPEC_VFM_FIRST
-#define SML_SPEC_VFM_FIRST 0
 #endif
 constexpr int kSpecStride = SML_SPEC_STRIDE;
 static_assert(kSpecStride >= kMX, "k_st_spec grid stride");
@@ -1602,6 +1638,7 @@ __global__ __launch_bounds__(kSpecBlk) void k_st_spec(
     // before the first MFMA, so the second tile costs no memory round trip of its own
     constexpr int kTiles = (kNFwd + 7) / 8, kWaves = kSpecBlk / 64;
     static_assert(kTiles <= 2 * kWaves, "specy: two tiles per wave at most");
+    static_assert(kTiles - kWaves <= kWaves / 2, "specy: the waves with two tiles are among those that load first");
     auto tile_load = [&](int tile, double (&vn)[kIY / 4], double (&vs)[kIY / 4]) {
         const int fa = tile * 8 + (r >> 1);
         const double *vr = vm + (fa < kNFwd ? fa : 0) * 2 + (r & 1);
@@ -1612,23 +1649,26 @@ __global__ __launch_bounds__(kSpecBlk) void k_st_spec(
             vs[s] = vr[j * kVLs];
         }
     };
-    // SML_SPEC_VFM_FIRST: specy's Fourier operands -- the hand-off from the row kernel,
-    // the loads specy waits on -- issued before the state / table loads (needed only
-    // after specy), so their memory round trip starts first
     double vn0[kIY / 4], vs0[kIY / 4], vn1[kIY / 4], vs1[kIY / 4];
     const bool two = wave + kWaves < kTiles;  // wave-uniform
-#if SML_SPEC_VFM_FIRST
-    tile_load(wave, vn0, vs0);
-    if (two) tile_load(wave + kWaves, vn1, vs1);
-#endif
     constexpr int RT = (kTabMDoubles / 2 + kSpecBlk - 1) / kSpecBlk;
     // three named registers, not an array: held across specy, an array was kept in scratch
     static_assert((RT == 2 || RT == 3) && 2 * RT * kSpecBlk <= kVFm && 2 * RT * kSpecBlk - kTabMDoubles <= kTabMPad,
                   "TabM staging");
     double2 rt0, rt1, rt2 = {0.0, 0.0};
-    // the m's state slice and tables: loads issued first, stored to LDS after specy
-    // (which reads its Fourier coefficients straight from vfm), so their latency
-    // hides behind it
+    // Load order.  The m's state slice, tables and forcing and specy's B operands -- all
+    // same-XCD L2 hits -- are issued first, the pinv slice after them.  Vector loads return
+    // in order, so the kernel waits on the first group alone (a counted vmcnt), stages it
+    // in LDS and runs the state-only half of the tail (tail_pre) before specy.  The
+    // prologue is bound by the issue of its loads -- the CU takes one vector-memory
+    // instruction of a wave per about 16 clocks; the Fourier tiles alone are 120 per
+    // block, 0.8 us -- and a wave that issues does nothing else.  So the row kernel's
+    // Fourier coefficients (tile_load) are issued behind the staging barrier in two
+    // orders: waves 0..3 load their tiles and then run tail_pre, waves 4..7 (the other
+    // wave of each SIMD) run tail_pre and then load: one half's f64 chains fill the other
+    // half's issue time.  (Every wave loading first, in front of the barrier or behind
+    // it: the kernel 0.2 us slower than / as long as with the tail in one piece,
+    // profiles/spec_kernel_pretail.md.)
     constexpr int NS = kSM / 2, RS = (NS + kSpecBlk - 1) / kSpecBlk;
     static_assert(RS == 5 && NS % kSpecBlk == 0, "state staging: five whole rows of the block");
     double2 rs0, rs1, rs2, rs3, rs4;  // named registers (an array held across specy went to scratch)
@@ -1646,35 +1686,90 @@ __global__ __launch_bounds__(kSpecBlk) void k_st_spec(
         rt1 = t[kSpecBlk];
         if constexpr (RT > 2) rt2 = t[2 * kSpecBlk];
     }
-    // the m's forcing (load_forcing_m's elements, one per thread) stays in a register
-    // until specy is done: stored to LDS here, its wait would have cost a memory
-    // round trip before specy's loads issued
+    // the m's forcing (load_forcing_m's elements, one per thread)
     double rf = 0.0;
     if (threadIdx.x < 3 * kCW) {
         const int which = threadIdx.x / kCW, cf = threadIdx.x % kCW;
         const double *src = which == 0 ? phis : which == 1 ? tcorh : qcorh;
         rf = src[ci(cf & 1, m, cf >> 1)];
     }
+    // specy's B operands: every wave's tiles use this m's Legendre columns of its lanes,
+    // packed in lane order (k_pack_pfwd), and the same Gaussian weights.  They are the same
+    // for all eight waves, so the block loads them once -- one 16-B piece of the 6 KB per
+    // thread of the first six waves, the 24 weights by 24 lanes -- and stages them in V
+    // behind the pinv slice; each wave reads its operands from LDS in front of its MFMAs.
+    // (Loaded by every wave they were 96 of the 171 vector-memory instructions in
+    // front of the tiles' loads, and the prologue is bound by their issue.)
+    constexpr int kPinvM = kNX * 32, kVPinv = 2 * RT * kSpecBlk;
+    constexpr int kPflM = 2 * (kIY / 4) * 64, kVPfl = kVPinv + kPinvM, kVWt = kVPfl + kPflM;
+    static_assert(kPinvM == 2 * kSpecBlk && kVPinv % 2 == 0, "pinv slice staging in V");
+    static_assert(kPflM / 2 <= kSpecBlk && kIY <= 64 && kVWt + kIY <= kVFm, "Legendre columns and weights staged in V");
+    double2 rl = {0.0, 0.0};
+    double rw = 0.0;
+    if (threadIdx.x < kPflM / 2)
+        rl = reinterpret_cast<const double2 *>(pfl)[(size_t)m * (kPflM / 2) + threadIdx.x];
+    if (threadIdx.x < kIY) rw = wt[threadIdx.x];
+    // (the scheduler would otherwise be free to sink these loads below specy's)
+    __builtin_amdgcn_sched_barrier(0);
     // gridy's Legendre slice of this m (8 KB, one 16-B load per thread), staged in V
     // behind the tables: each wave then reads its MFMA operands from LDS instead of
     // every wave fetching the same 8 KB from memory in the gridy phase
-    constexpr int kPinvM = kNX * 32, kVPinv = 2 * RT * kSpecBlk;
-    static_assert(kPinvM == 2 * kSpecBlk && kVPinv + kPinvM <= kVFm && kVPinv % 2 == 0, "pinv slice staging in V");
     const double2 rp = reinterpret_cast<const double2 *>(pinv + (size_t)m * kPinvM)[threadIdx.x];
-    // specy operands: wave w's tiles all use this m's Legendre columns of its lanes,
-    // packed in lane order (k_pack_pfwd): one contiguous 1-KB load per k-step instead
-    // of two loads touching 16 lines each (the prologue is bound by its loads' lines)
-    const double2 *pl = reinterpret_cast<const double2 *>(pfl) + (size_t)m * (kIY / 4) * 64 + l;
+    // (these loads stay ahead of the first wait)
+    __builtin_amdgcn_sched_barrier(0);
+    if (dbg) __syncthreads();
+    stamp(dbg, sk, 1);
+    // (stamps: "load", 0 to 1, is the issue of the loads above; the staging, tail_pre and
+    // the tiles' loads fall into "specy", 1 to 2; "tail", 3 to 4, is tail_post alone)
+    // state, tables, forcing and specy's B operands into LDS: the wait in front of these
+    // stores leaves the pinv slice outstanding
+    TabM *tm = reinterpret_cast<TabM *>(V);
+    {
+        double2 *v2 = reinterpret_cast<double2 *>(V) + threadIdx.x;  // (V holds kVFm >= 2 RT kSpecBlk doubles)
+        v2[0] = rt0;
+        v2[kSpecBlk] = rt1;
+        if constexpr (RT > 2) v2[2 * kSpecBlk] = rt2;
+        double2 *s2 = reinterpret_cast<double2 *>(Sst) + threadIdx.x;
+        s2[0] = rs0;
+        s2[kSpecBlk] = rs1;
+        s2[2 * kSpecBlk] = rs2;
+        s2[3 * kSpecBlk] = rs3;
+        s2[4 * kSpecBlk] = rs4;
+        if (threadIdx.x < 3 * kCW) Fm[threadIdx.x] = rf;
+        if (threadIdx.x < kPflM / 2) reinterpret_cast<double2 *>(V + kVPfl)[threadIdx.x] = rl;
+        if (threadIdx.x < kIY) V[kVWt + threadIdx.x] = rw;
+    }
+    __syncthreads();  // Sst, Fm, the tables, the Legendre columns and weights complete
+    const LTab tb{tm};
+    static_assert(kSpecBlk == kSpecThreads, "k_st_spec: one thread per (coefficient, level), none idle in the tail");
+    const int cc = threadIdx.x & (kCW - 1), k = wave;
+    const int n = cc >> 1, p = cc & 1;
+    const int c = ci(p, m, n);
+    // c0) the tail's state-only half.  The whole m's state is in LDS, so the other levels'
+    // div and t are read from Sst directly: no copy into sh, no second barrier.  Sst is
+    // next written by tail_post's timint, behind the barrier that follows specy.
+    auto SA = [&](int var, int lev, int kk2) -> double & { return Sst[smi(var, lev, kk2, cc)]; };
+    const bool loads_first = wave < kWaves / 2;  // wave-uniform: the two waves of a SIMD take opposite orders
+    if (loads_first) {
+        tile_load(wave, vn0, vs0);
+        if (two) tile_load(wave + kWaves, vn1, vs1);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    const TailPre pre = tail_pre<true>(SA, [&](int v, int kk2) { return Sst[smi(1 + v, j4, kk2, cc)]; },
+                                       lead && next_j2 <= 0 ? phi_out : nullptr, Fm, Fm + kCW, Fm + 2 * kCW, cc, tb, k,
+                                       c, m, n, j4);
+    // (tail_pre stays ahead of the other waves' loads, of specy's wait and of its MFMAs)
+    __builtin_amdgcn_sched_barrier(0);
+    if (!loads_first) tile_load(wave, vn0, vs0);  // (one tile: static_assert above)
+    __builtin_amdgcn_sched_barrier(0);
     double wv[kIY / 4], bS[kIY / 4], bD[kIY / 4];
 #pragma unroll
     for (int s = 0; s < kIY / 4; ++s) {
-        const double2 b = pl[s * 64];
-        wv[s] = wt[4 * s + kk];
+        const double2 b = reinterpret_cast<const double2 *>(V + kVPfl)[s * 64 + l];
+        wv[s] = V[kVWt + 4 * s + kk];
         bS[s] = b.x;
         bD[s] = b.y;
     }
-    if (dbg) __syncthreads();
-    stamp(dbg, sk, 1);
     auto tile_mma = [&](int tile, const double (&vn)[kIY / 4], const double (&vs)[kIY / 4]) {
         const int f0 = tile * 8;
         // the lanes of fields >= kNFwd (the last tile's) loaded field 0 (tile_load: in
@@ -1698,38 +1793,13 @@ __global__ __launch_bounds__(kSpecBlk) void k_st_spec(
             S[f * kCW + 2 * (2 * r + 1) + (row & 1)] = accD[q];
         }
     };
-    {
-#if !SML_SPEC_VFM_FIRST
-        tile_load(wave, vn0, vs0);
-        if (two) tile_load(wave + kWaves, vn1, vs1);
-#endif
-        tile_mma(wave, vn0, vs0);
-        if (two) tile_mma(wave + kWaves, vn1, vs1);
-    }
-    TabM *tm = reinterpret_cast<TabM *>(V);
-    {
-        double2 *v2 = reinterpret_cast<double2 *>(V) + threadIdx.x;  // (V holds kVFm >= 2 RT kSpecBlk doubles)
-        v2[0] = rt0;
-        v2[kSpecBlk] = rt1;
-        if constexpr (RT > 2) v2[2 * kSpecBlk] = rt2;
-        double2 *s2 = reinterpret_cast<double2 *>(Sst) + threadIdx.x;
-        s2[0] = rs0;
-        s2[kSpecBlk] = rs1;
-        s2[2 * kSpecBlk] = rs2;
-        s2[3 * kSpecBlk] = rs3;
-        s2[4 * kSpecBlk] = rs4;
-        if (threadIdx.x < 3 * kCW) Fm[threadIdx.x] = rf;
-        reinterpret_cast<double2 *>(V + kVPinv)[threadIdx.x] = rp;
-    }
-    __syncthreads();  // S, Sst, Fm, the tables complete
-    const LTab tb{tm};
+    tile_mma(wave, vn0, vs0);
+    if (two) tile_mma(wave + kWaves, vn1, vs1);
+    reinterpret_cast<double2 *>(V + kVPinv)[threadIdx.x] = rp;  // (behind the tables: no reader before gridy)
+    __syncthreads();  // S and the pinv slice complete
     stamp(dbg, sk, 2);
     // b) combine (k_dyn_combine) for coefficient (n, p) at level k: every thread of the
     // block holds one, k the wave's index (wave-uniform)
-    static_assert(kSpecBlk == kSpecThreads, "k_st_spec: one thread per (coefficient, level), none idle in the tail");
-    const int cc = threadIdx.x & (kCW - 1), k = wave;
-    const int n = cc >> 1, p = cc & 1;
-    const int c = ci(p, m, n);
     auto fl = [&](int f) { return [=](int pp, int nn) { return S[f * kCW + 2 * nn + pp]; }; };
     double vo = 0.0, dv = 0.0, d0 = 0.0, dq = 0.0, dummy;
     vds_gen(fl(k), fl(3 * kKX + k), tb, n, p, &vo, &dv);  // vdspec(utend, vtend)
@@ -1742,10 +1812,10 @@ __global__ __launch_bounds__(kSpecBlk) void k_st_spec(
         __syncthreads();
         stamp(dbg, sk, 3);
     }
-    // c) sptend / implic / diffusion / time integration on the LDS state
-    auto SA = [&](int var, int lev, int kk2) -> double & { return Sst[smi(var, lev, kk2, cc)]; };
-    tail_coef<kCW, true>(SA, lead ? Td : nullptr, lead && next_j2 <= 0 ? phi_out : nullptr, Fm, Fm + kCW, Fm + 2 * kCW,
-                         cc, tb, sh, cc, k, c, m, n, vo, dv - lapv, tdt0, trdt0, psdt, j1, j4, dt, alph, rob, wil);
+    // c) the tail's other half: sptend's corrections / implic / diffusion / time
+    // integration on the LDS state
+    tail_post<kCW>(SA, pre, lead ? Td : nullptr, tb, sh, cc, k, c, m, n, vo, dv - lapv, tdt0, trdt0, psdt, j1, dt, alph,
+                   rob, wil);
     __syncthreads();  // S is free, Sst complete
     stamp(dbg, sk, 4);
     if (next_j2 <= 0) {  // the run of fused steps ends: the state straight into the reference layout
