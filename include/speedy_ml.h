@@ -212,13 +212,46 @@ int sml_res_set_read_waves(sml_reservoirs *c, int waves);
  * (SML_RES_PATH_PER_REGION), the v_p finish one thread per output instead of in
  * column groups (SML_RES_PATH_UNGROUPED_FINISH), the training drive one update launch
  * per column after a column-writer launch instead of one persistent launch per batch
- * (SML_RES_PATH_STEPWISE_DRIVE).  For tests and for a host bisecting a
- * difference; 0 restores the defaults. */
+ * (SML_RES_PATH_STEPWISE_DRIVE), sml_res_spectral_radius's vectors in the context's
+ * global scratch instead of LDS (SML_RES_PATH_RADIUS_GLOBAL).  For tests and for a
+ * host bisecting a difference; 0 restores the defaults. */
 #define SML_RES_PATH_CSR 1
 #define SML_RES_PATH_PER_REGION 2
 #define SML_RES_PATH_UNGROUPED_FINISH 4
 #define SML_RES_PATH_STEPWISE_DRIVE 8
+#define SML_RES_PATH_RADIUS_GLOBAL 16
 int sml_res_set_reference_paths(sml_reservoirs *c, int flags);
+/* The spectral radius of every local region's A as loaded: gen_res's sparse_eigen
+ * (src/mod_reservoir.f90:190; ARPACK dnaupd / dneupd, src/mod_linalg.f90:219-514)
+ * for a matrix with no negative entry, which makesparse's is (RANDOM_NUMBER values,
+ * src/mod_linalg.f90:191).  Power iteration from x = 1 in the max norm, at most
+ * max_iter times:
+ *   y = A x      each row summed in the order of its entries, fp64
+ *   lo = min, hi = max of y_i / x_i over the rows with x_i > 0
+ *   m = max y_i; m == 0 ends with SML_RADIUS_ZERO; x = y / m
+ *   hi - lo <= tol * hi ends with SML_RADIUS_OK
+ * With x > 0, lo <= rho(A) <= hi (Collatz-Wielandt), so the two outputs enclose the
+ * radius up to the rounding of the row sums; min and max leave no summation order
+ * open, so the outputs are the same bits on every path.  One launch, a workgroup per
+ * region, x and y in LDS where 2 n doubles fit, else in a scratch of the context.
+ * lo, hi, iters, info: host arrays of nlocal, filled when the call returns (it waits
+ * for `stream`: a set-up call).  A negative or non-finite entry gives that region
+ * SML_RADIUS_INVALID; the other regions are not affected. */
+#define SML_RADIUS_OK 0      /* hi - lo <= tol * hi */
+#define SML_RADIUS_MAXITER 1 /* lo, hi are the last iteration's */
+#define SML_RADIUS_ZERO 2    /* A x vanished: lo = hi = 0 */
+#define SML_RADIUS_INVALID 3 /* a negative or non-finite entry: lo = hi = NaN */
+int sml_res_spectral_radius(sml_reservoirs *c, double tol, int max_iter, double *lo, double *hi, int *iters,
+                            int *info, void *stream);
+/* One region's untrained reservoir on the host, no GPU: makesparse's A before gen_res
+ * scales it (src/mod_linalg.f90:180-218, shuffle: src/mod_utilities.f90:1562-1589) and
+ * train_reservoir's block-diagonal W_in (src/mod_reservoir.f90:260-278), from a
+ * counter-based generator keyed by (seed, region) alone -- the recipe is in
+ * csrc/sml_genres.cpp.  rows / cols [k] 1-based, vals [k] in [0, 1) on the 2^-24 grid;
+ * row r of W_in holds win_val[r] (never 0, |.| <= sigma) in column win_col[r] = r / (n / ninp).
+ * n in 1..65535, k >= 0, ninp >= 1 dividing n, region >= 0; else SML_ERR_ARG. */
+int sml_gen_region(int n, int k, int ninp, uint64_t seed, int region, double sigma, int *rows, int *cols,
+                   float *vals, int *win_col, float *win_val);
 /* the number of CUs the context's launches get (its stream's CU mask; 0 = the whole
  * device): the balanced state update runs one block per CU over equal shares of all
  * local rows.  sml_res_update_balanced: 1 when the update takes that form (every

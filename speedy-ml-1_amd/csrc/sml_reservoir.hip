@@ -144,6 +144,13 @@ struct sml_reservoirs {
     // (k_drive_record), instead of k_res_drive: forced (sml_res_set_reference_paths), or
     // taken where a region does not fit k_res_drive's LDS
     bool stepwise_drive = false;
+    // sml_res_spectral_radius (k_res_radius): x and y in d_rad_xy ([2 * row0[r]]: x then y
+    // of region r; allocated at the first call that needs it) instead of LDS -- forced
+    // (sml_res_set_reference_paths), or taken by a region whose 2 n doubles exceed max_lds.
+    // d_rad_part [nlocal][3][16]: the waves' partial min / max; d_rad_out [nlocal] results
+    bool radius_global = false;
+    double *d_rad_xy = nullptr, *d_rad_part = nullptr;
+    void *d_rad_out = nullptr;
     int32_t *d_tgt_idx = nullptr;  // [nlocal][nout] the targets' positions in each region's feedback
     // the next grid finish waits in-kernel for *fin_wflag >= fin_wval (sml::res_finish_wait)
     const uint64_t *fin_wflag = nullptr;
@@ -608,6 +615,126 @@ __global__ __launch_bounds__(256) void k_drive_record(const RegionDev *__restric
     if (targets && blockIdx.y == 0) {
         double *tcol = targets + ((int64_t)m * r + c) * nout;
         for (int t = threadIdx.x; t < nout; t += blockDim.x) tcol[t] = u[rg.fb + tgt_idx[(size_t)r * nout + t]];
+    }
+}
+
+// ---------------------------------------------------------------- spectral radius
+// sml_res_spectral_radius: gen_res's sparse_eigen (src/mod_reservoir.f90:190) for the
+// matrices makesparse builds -- no negative entry, so the dominant eigenvalue is real
+// and simple (Perron-Frobenius) and plain power iteration finds it; the
+// Collatz-Wielandt ratios min / max of (A x)_i / x_i enclose it at every iteration
+// (DESIGN.md "Reservoir generation").  A block per region, the whole iteration in one
+// launch: x and y in LDS (or, same body, in the context's scratch), two block barriers
+// per iteration, no communication between blocks.  The norm is max |y_i| and the
+// enclosure a min and a max: no sum whose order could differ between forms.  The
+// waves' partial min / max go through global memory (d_rad_part), because at n = 10240
+// x and y take the whole 160 KiB of LDS; __syncthreads orders them within the block.
+struct RadiusOut {
+    double lo, hi;
+    int32_t iters, info;
+};
+
+constexpr int kRadWaves = kUpdThreads / 64;
+
+template <typename WT>
+__device__ __attribute__((always_inline)) inline void radius_region(const int32_t *__restrict__ rp,
+                                                                    const uint16_t *__restrict__ ac,
+                                                                    const WT *__restrict__ av, int n, double *x,
+                                                                    double *y, double *pw, double tol, int max_iter,
+                                                                    RadiusOut *out) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    // a negative or non-finite entry: Perron-Frobenius does not hold, nothing is iterated
+    // (the block's "any" goes through the partials like the min / max below: no
+    // __syncthreads_or, whose static LDS would not fit beside 160 KiB of x and y)
+    int bad = 0;
+    for (int e = tid, e1 = rp[n]; e < e1; e += kUpdThreads) {
+        const double v = (double)av[e];
+        bad |= !(v >= 0.0 && v <= 1.7976931348623157e308);
+    }
+    bad = __any(bad);
+    if (lane == 0) pw[wave] = bad ? 1.0 : 0.0;
+    __syncthreads();
+    double anybad = pw[lane % kRadWaves];
+    for (int o = kRadWaves / 2; o > 0; o >>= 1) anybad = fmax(anybad, __shfl_xor(anybad, o));
+    if (anybad > 0.0) {  // block-uniform
+        if (tid == 0) *out = RadiusOut{__builtin_nan(""), __builtin_nan(""), 0, SML_RADIUS_INVALID};
+        return;
+    }
+    for (int i = tid; i < n; i += kUpdThreads) x[i] = 1.0;
+    __syncthreads();  // x complete; the flags read by every wave before the partials reuse them
+    double lo = 0.0, hi = 0.0;
+    int info = SML_RADIUS_MAXITER, t = 1;
+    for (;; ++t) {  // (lo, hi, the norm and so every branch below are block-uniform)
+        double tlo = __builtin_inf(), thi = 0.0, tm = 0.0;
+        for (int i = tid; i < n; i += kUpdThreads) {
+            double s = 0.0;
+            for (int e = rp[i], e1 = rp[i + 1]; e < e1; ++e) s = s + (double)av[e] * x[ac[e]];
+            y[i] = s;
+            const double xi = x[i];
+            if (xi > 0.0) {
+                const double q = s / xi;
+                tlo = fmin(tlo, q);
+                thi = fmax(thi, q);
+            }
+            tm = fmax(tm, s);
+        }
+        for (int o = 32; o > 0; o >>= 1) {
+            tlo = fmin(tlo, __shfl_xor(tlo, o));
+            thi = fmax(thi, __shfl_xor(thi, o));
+            tm = fmax(tm, __shfl_xor(tm, o));
+        }
+        if (lane == 0) {
+            pw[wave] = tlo;
+            pw[kRadWaves + wave] = thi;
+            pw[2 * kRadWaves + wave] = tm;
+        }
+        __syncthreads();  // y and the partials complete; every read of x done
+        lo = pw[lane % kRadWaves];
+        hi = pw[kRadWaves + lane % kRadWaves];
+        double m = pw[2 * kRadWaves + lane % kRadWaves];
+        for (int o = kRadWaves / 2; o > 0; o >>= 1) {
+            lo = fmin(lo, __shfl_xor(lo, o));
+            hi = fmax(hi, __shfl_xor(hi, o));
+            m = fmax(m, __shfl_xor(m, o));
+        }
+        if (m == 0.0) {
+            lo = hi = 0.0;
+            info = SML_RADIUS_ZERO;
+            break;
+        }
+        if (hi - lo <= tol * hi) {
+            info = SML_RADIUS_OK;
+            break;
+        }
+        if (t == max_iter) break;
+        for (int i = tid; i < n; i += kUpdThreads) x[i] = y[i] / m;
+        __syncthreads();  // x complete; the partials read by every wave
+    }
+    if (tid == 0) *out = RadiusOut{lo, hi, t, info};
+}
+
+// lds_limit: the bytes of LDS a region's 2 n doubles may take (0 forces the scratch)
+template <typename WT>
+__global__ __launch_bounds__(kUpdThreads) void k_res_radius(const RegionDev *__restrict__ R,
+                                                            const int32_t *__restrict__ row0,
+                                                            const int32_t *__restrict__ a_rp,
+                                                            const uint16_t *__restrict__ a_col,
+                                                            const WT *__restrict__ a_val, double *xy, double *part,
+                                                            RadiusOut *out, double tol, int max_iter,
+                                                            size_t lds_limit) {
+    extern __shared__ __attribute__((aligned(16))) double smem[];
+    const int r = blockIdx.x;
+    const RegionDev rg = R[r];
+    const int n = rg.n;
+    const int32_t *rp = a_rp + rg.a_rp;
+    const uint16_t *ac = a_col + rg.a_nz;
+    const WT *av = a_val + rg.a_nz;
+    double *pw = part + (size_t)r * 3 * kRadWaves;
+    if (2 * (size_t)n * sizeof(double) <= lds_limit) {  // block-uniform
+        radius_region<WT>(rp, ac, av, n, smem, smem + n, pw, tol, max_iter, out + r);
+    } else {
+        double *x = xy + 2 * (int64_t)row0[r];
+        radius_region<WT>(rp, ac, av, n, x, x + n, pw, tol, max_iter, out + r);
     }
 }
 
@@ -1616,7 +1743,7 @@ extern "C" int sml_res_destroy(sml_reservoirs *c) {
                     c->d_wout,  c->d_x[0],    c->d_x[1],   c->d_meanstd, c->d_outl,  c->d_asm_dst,
                     c->d_fb_src, c->d_fb_l,   c->d_fb_reg, c->d_lm_src, c->d_lm_l,   c->d_io,     c->d_part,
                     c->d_wlm,   c->d_tisr_fb, c->d_tisr_grid, c->d_tisr_reg, c->d_row0, c->d_blk_r0,
-                    c->d_tgt_idx};
+                    c->d_tgt_idx, c->d_rad_xy, c->d_rad_part, c->d_rad_out};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
     for (hipEvent_t e : c->ev)
@@ -1939,9 +2066,10 @@ extern "C" int sml_res_ell_layout(sml_reservoirs *c, int i, int *a_width, int *a
 // their CSR copies, no ELL layout (before any region is loaded); SML_RES_PATH_PER_REGION
 // -- k_res_update, a block per (region, part), instead of the balanced update;
 // SML_RES_PATH_UNGROUPED_FINISH -- the v_p finish one thread per output;
-// SML_RES_PATH_STEPWISE_DRIVE -- the training drive one update launch per column
+// SML_RES_PATH_STEPWISE_DRIVE -- the training drive one update launch per column;
+// SML_RES_PATH_RADIUS_GLOBAL -- the spectral radius's x and y in the context's scratch
 extern "C" int sml_res_set_reference_paths(sml_reservoirs *c, int flags) {
-    SML_REQUIRE(c && (flags & ~15) == 0, "bad argument");
+    SML_REQUIRE(c && (flags & ~31) == 0, "bad argument");
     const bool csr = flags & SML_RES_PATH_CSR;
     if (csr != c->no_ell) {
         for (unsigned char l : c->loaded)
@@ -1958,6 +2086,7 @@ extern "C" int sml_res_set_reference_paths(sml_reservoirs *c, int flags) {
     c->upd_bal = !(flags & SML_RES_PATH_PER_REGION);
     c->finish_ungrouped = flags & SML_RES_PATH_UNGROUPED_FINISH;
     c->stepwise_drive = flags & SML_RES_PATH_STEPWISE_DRIVE;
+    c->radius_global = flags & SML_RES_PATH_RADIUS_GLOBAL;
     return SML_OK;
 }
 
@@ -2479,6 +2608,63 @@ extern "C" int sml_res_train_drive(sml_reservoirs *c, const double *d_inputs, in
         go(double{});
     SML_HIP(hipGetLastError());
     c->cur = 1 - c->cur;
+    return SML_OK;
+}
+
+// the spectral radius of every local region's A (k_res_radius above): one launch, then
+// the host waits for the stream -- a set-up call, not part of the step
+extern "C" int sml_res_spectral_radius(sml_reservoirs *c, double tol, int max_iter, double *lo, double *hi,
+                                       int *iters, int *info, void *stream) {
+    SML_REQUIRE(c != nullptr, "null reservoir context");
+    SML_REQUIRE(tol > 0.0, "sml_res_spectral_radius: tol must be positive");  // (a NaN fails it too)
+    SML_REQUIRE(max_iter >= 1, "sml_res_spectral_radius: max_iter = %d < 1", max_iter);
+    if (c->nlocal == 0) return SML_OK;
+    SML_REQUIRE(lo && hi && iters && info, "sml_res_spectral_radius: null output array");
+    if (int rc = check_loaded(c)) return rc;
+    // x and y of a region in LDS where they fit (and the scratch is not forced); the
+    // kernel keeps no static LDS, but what the compiler reports is taken off the limit
+    hipFuncAttributes fa;
+    if (c->wdtype == SML_F32)
+        SML_HIP(hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(&k_res_radius<float>)));
+    else
+        SML_HIP(hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(&k_res_radius<double>)));
+    const size_t lds_limit = c->radius_global || fa.sharedSizeBytes > c->max_lds ? 0 : c->max_lds - fa.sharedSizeBytes;
+    size_t lds = 0;
+    bool scratch = false;
+    for (int i = 0; i < c->nlocal; ++i) {
+        const size_t b = 2 * (size_t)c->n[i] * sizeof(double);
+        if (b <= lds_limit)
+            lds = std::max(lds, b);
+        else
+            scratch = true;
+    }
+    if (!c->d_rad_part) {
+        if (int rc = dalloc(&c->d_rad_part, (size_t)c->nlocal * 3 * kRadWaves)) return rc;
+        if (int rc = dalloc_bytes(&c->d_rad_out, (size_t)c->nlocal * sizeof(RadiusOut))) return rc;
+    }
+    if (scratch && !c->d_rad_xy)
+        if (int rc = dalloc(&c->d_rad_xy, 2 * (size_t)c->row0_h[c->nlocal])) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    auto go = [&](auto wt_tag) {
+        using WT = decltype(wt_tag);
+        hipLaunchKernelGGL(k_res_radius<WT>, dim3(c->nlocal), dim3(kUpdThreads), lds, st, c->d_rd, c->d_row0,
+                           c->d_a_rp, c->d_a_col, (const WT *)c->d_a_val, c->d_rad_xy, c->d_rad_part,
+                           (RadiusOut *)c->d_rad_out, tol, max_iter, lds_limit);
+    };
+    if (c->wdtype == SML_F32)
+        go(float{});
+    else
+        go(double{});
+    SML_HIP(hipGetLastError());
+    SML_HIP(hipStreamSynchronize(st));
+    std::vector<RadiusOut> out(c->nlocal);
+    SML_HIP(hipMemcpy(out.data(), c->d_rad_out, out.size() * sizeof(RadiusOut), hipMemcpyDeviceToHost));
+    for (int i = 0; i < c->nlocal; ++i) {
+        lo[i] = out[i].lo;
+        hi[i] = out[i].hi;
+        iters[i] = out[i].iters;
+        info[i] = out[i].info;
+    }
     return SML_OK;
 }
 

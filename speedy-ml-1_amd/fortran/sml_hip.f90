@@ -618,6 +618,32 @@ module sml_hip
       integer(c_int64_t), value :: stride, model_stride
       integer(c_int) :: rc
     end function
+    !> the spectral radius of every local region's A (gen_res's sparse_eigen,
+    !> mod_reservoir.f90:190): lo <= rho <= hi per region, info 0 when hi - lo <= tol * hi;
+    !> host arrays of nlocal, filled when the call returns
+    function sml_res_spectral_radius(ctx, tol, max_iter, lo, hi, iters, info, stream) &
+        bind(C, name='sml_res_spectral_radius') result(rc)
+      import :: c_ptr, c_int, c_double
+      type(c_ptr), value :: ctx, stream
+      real(c_double), value :: tol
+      integer(c_int), value :: max_iter
+      real(c_double), intent(out) :: lo(*), hi(*)
+      integer(c_int), intent(out) :: iters(*), info(*)
+      integer(c_int) :: rc
+    end function
+    !> makesparse's A before gen_res scales it and train_reservoir's W_in for one region
+    !> (mod_linalg.f90:180-218, mod_reservoir.f90:260-278), host only: rows / cols 1-based,
+    !> vals in [0, 1), row r of W_in = win_val(r) in the 0-based column win_col(r)
+    function sml_gen_region(n, k, ninp, seed, region, sigma, rows, cols, vals, win_col, win_val) &
+        bind(C, name='sml_gen_region') result(rc)
+      import :: c_int, c_int64_t, c_double, c_float
+      integer(c_int), value :: n, k, ninp, region
+      integer(c_int64_t), value :: seed
+      real(c_double), value :: sigma
+      integer(c_int), intent(out) :: rows(*), cols(*), win_col(*)
+      real(c_float), intent(out) :: vals(*), win_val(*)
+      integer(c_int) :: rc
+    end function
     !> processor_decomposition (res_domain.f90:31-62), 0-based regions
     function sml_processor_decomposition(numregions, numprocs, irank, regions, count) &
         bind(C, name='sml_processor_decomposition') result(rc)

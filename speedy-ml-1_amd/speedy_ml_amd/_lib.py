@@ -64,12 +64,15 @@ EXPORTED = (
     "sml_hybrid_set_calendar", "sml_hybrid_window_date", "sml_hybrid_set_hop_timeout",
     "sml_dyn_set_check_timeout", "sml_dyn_check_stream", "sml_dyn_set_fused", "sml_res_set_reference_paths",
     "sml_train_set_panel", "sml_res_train_drive", "sml_region_target_index",
+    "sml_res_spectral_radius", "sml_gen_region",
 )
 
 SML_HOP_AUTO, SML_HOP_WAIT_VALUE, SML_HOP_EVENTS, SML_HOP_KERNEL = 0, 1, 2, 3
 SML_CHAIN_AUTO, SML_CHAIN_TWO_STREAMS, SML_CHAIN_SPEEDY = 0, 1, 2
 SML_RES_PATH_CSR, SML_RES_PATH_PER_REGION, SML_RES_PATH_UNGROUPED_FINISH = 1, 2, 4
 SML_RES_PATH_STEPWISE_DRIVE = 8
+SML_RES_PATH_RADIUS_GLOBAL = 16
+SML_RADIUS_OK, SML_RADIUS_MAXITER, SML_RADIUS_ZERO, SML_RADIUS_INVALID = 0, 1, 2, 3
 
 
 class SmlError(RuntimeError):
@@ -268,6 +271,8 @@ def _declare(L: ctypes.CDLL) -> None:
         "sml_hybrid_set_hop_timeout": [vp, ctypes.c_int64],
         "sml_res_train_drive": [vp, vp, i, ctypes.c_int64, vp, ctypes.c_int64, vp, vp, vp],
         "sml_region_target_index": [i, i, i, vp, ip],
+        "sml_res_spectral_radius": [vp, d, i, vp, vp, vp, vp, vp],
+        "sml_gen_region": [i, i, i, ctypes.c_uint64, i, d, vp, vp, vp, vp, vp],
     }
     for name, args in sig.items():
         if os.environ.get("SML_LIB") and not hasattr(L, name):

@@ -157,14 +157,28 @@ class Reservoirs:
         return dict(a_width=v[0].value, a_overflow=bool(v[1].value), win_q=v[2].value, win_ell=bool(v[3].value))
 
     def set_reference_paths(self, csr: bool = False, per_region: bool = False, ungrouped_finish: bool = False,
-                            stepwise_drive: bool = False):
+                            stepwise_drive: bool = False, radius_global: bool = False):
         """Force the fallback paths for every region (sml_res_set_reference_paths): A /
         W_in from their CSR copies (before any region is loaded), the per-region state
         update, the v_p finish one thread per output, the training drive one update
-        launch per column -- bitwise the defaults."""
+        launch per column, spectral_radius's vectors in global scratch -- bitwise the
+        defaults."""
         flags = ((1 if csr else 0) | (2 if per_region else 0) | (4 if ungrouped_finish else 0)
-                 | (8 if stepwise_drive else 0))
+                 | (8 if stepwise_drive else 0) | (16 if radius_global else 0))
         check(lib().sml_res_set_reference_paths(self._h, flags))
+
+    def spectral_radius(self, tol: float = 2e-14, max_iter: int = 1000, stream=None):
+        """The spectral radius of every local region's A as loaded (sml_res_spectral_radius;
+        gen_res's sparse_eigen, mod_reservoir.f90:190): power iteration with the
+        Collatz-Wielandt enclosure lo <= rho <= hi, for A without negative entries.
+        Returns (lo, hi, iters, info), arrays of nlocal; info 0 = hi - lo <= tol * hi,
+        1 = max_iter reached, 2 = A x vanished, 3 = a negative or non-finite entry.
+        Waits for the stream."""
+        lo, hi = np.zeros(self.nlocal), np.zeros(self.nlocal)
+        iters, info = np.zeros(self.nlocal, dtype=np.int32), np.zeros(self.nlocal, dtype=np.int32)
+        check(lib().sml_res_spectral_radius(self._h, float(tol), int(max_iter), ptr(lo), ptr(hi), ptr(iters),
+                                            ptr(info), stream_ptr(stream)))
+        return lo, hi, iters, info
 
     def target_index(self, i: int) -> np.ndarray:
         """0-based positions of local region i's training targets inside its feedback

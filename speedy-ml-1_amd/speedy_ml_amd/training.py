@@ -90,8 +90,9 @@ class Trainer:
 def train_wout(res, d_inputs, d_model, discard: int, batch: int, nbatches: int, ncs: int = 132,
                beta_res: float = 0.001, beta_model: float = 1.0, using_prior: bool = True, prior_val: float = 0.0,
                dtype=np.float32, stream=None):
-    """Train W_out of every local region of `res` (a Reservoirs with A and W_in loaded)
-    from a training series on the device: the reference's train_reservoir tail,
+    """Train W_out of every local region of `res` (a Reservoirs with A and W_in loaded:
+    genres.generate draws them and scales A to its spectral radius, gen_res + the W_in
+    fill of train_reservoir) from a training series on the device: the reference's train_reservoir tail,
     reservoir_layer_chunking_hybrid + chunking_matmul + fit_chunk_hybrid
     (src/mod_reservoir.f90:1065-1173, :1643-1699, :1233-1332).
 
