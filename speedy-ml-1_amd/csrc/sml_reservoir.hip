@@ -32,6 +32,7 @@
 #include <vector>
 
 #include "sml_internal.hpp"
+#include "sml_reservoir_layout.hpp"
 #include "sml_timeline.hpp"
 
 SML_TL_DEFINE(reservoir)
@@ -47,59 +48,26 @@ using namespace sml;
 
 namespace {
 
-constexpr int kLdAlign = 32;    // W_out / x_aug row stride multiple (columns)
-constexpr int kRows = 8;        // W_out rows per wave in the readout (nout_pad's multiple)
 constexpr int kRowsWide = 17;   // rows per wave when nout_pad = 17 w (w <= 8 waves)
 constexpr int kWideWaves = 2;   // waves per readout block with kRowsWide rows (a region = w / 2 blocks;
                                 // 2 / 4 / 8 waves measured: one-pass 0.638 / 0.644 / 0.696 ms)
 constexpr int kMaxNcs = 256;     // local-model length bound of the fused finish (132 in T30L8)
-constexpr int kMeanStd = 36;    // mean/std vector length (mod_reservoir.f90:1815-1846)
-constexpr int kTisrStride = 16; // packed tisr input: [nlocal][16]
-constexpr int kSrcKeep = -1;    // feedback entry left untouched (sst)
-
-constexpr int kEllA = 8;  // ELL slots reserved per row for A (makesparse rows hold floor(k/n) or +1 <= 8)
-constexpr int kEllW = 1;  // ELL slots per row for W_in (the trained W_in has one entry per row)
-
-// A's ELL copy (r04b): a_w "main" slots per row, stored as slot pairs, pair-major
-// ([pair][n] of (col, col) u16 pairs and of (val, val) pairs: lane i's row is one
-// 4-B + one 8-B load per pair, coalesced across the wave), a_w chosen per region to
-// move the fewest bytes.  makesparse rows hold floor(k/n) or floor(k/n) + 1 entries
-// (mod_linalg.f90:180-218): with a_ov the rows holding a_w + 1 keep their last entry
-// in an overflow list instead of padding every row to the longest -- a bit per row
-// (u64 words) + a count per word locate it.  The dominant 4x4+sst region (n 6048,
-// 4.8 % of rows one longer) moves 36.5 B of A per row instead of 48.
-struct RegionDev {
-    int n, ninp, ld;
-    int a_w, w_w;  // A's ELL main width in slots (0 = use the CSR copy); W_in ELL (1) or CSR (0)
-    int a_ov;      // 1: rows of a_w + 1 entries, the last in the overflow list
-    int w_q;       // > 0: W_in's column of row i is i / w_q = umulhi(i, w_magic), not stored
-    uint32_t w_magic;
-    int64_t a_rp, a_nz, w_rp, w_nz, wout, x, xaug, fb;
-    int64_t wlm;  // W_out(:, 1:ncs) transposed, [ncs][nout_pad], in the W_out pool after the row-major blocks
-    int64_t a_ell, w_ell;  // offsets into the ELL pools (A: pair-major as above; W_in: [n])
-    int64_t a_om;          // overflow bit words / per-word counts: [ceil(n / 64)] each
-    int64_t a_oe;          // overflow entries (col, val) in row order: [n] reserved
-};
 
 }  // namespace
 
-struct sml_reservoirs {
+// (PoolPlan: rd, ld, the ELL caps, the pools' sizes tot_*, maxn / maxninp -- plan_pools)
+struct sml_reservoirs : PoolPlan {
     int numregions = 0, nlocal = 0, ncs = 0, nout = 0, nout_pad = 0, wdtype = SML_F32;
     // row stride of the outvec arrays (sml_res_set_outvec_ld): nout, or wider when the
     // hybrid loop carries the slab ocean's sst beside each outvec in its exchange rows
     int ov_ld = 0;
     double leakage = 1.0;
-    std::vector<int> region_ids, n, k, ninp, ld;
+    std::vector<int> region_ids, n, k, ninp;
     std::vector<unsigned char> sst, loaded;
     std::vector<RegionGeom> geom;
-    std::vector<RegionDev> rd;
-    int64_t tot_wlm = 0;  // elements of the transposed local-model blocks (pool d_wlm)
     void *d_wlm = nullptr;
-    int64_t tot_a_rp = 0, tot_a_nz = 0, tot_w_rp = 0, tot_w_nz = 0, tot_wout = 0, tot_xaug = 0,
-            tot_fb = 0;
     std::vector<int64_t> w_nz_cap;  // reserved W_in CSR nnz per region (n at create: one entry per row as
                                     // trained; grow_win_pool re-lays the pool for a denser W_in)
-    int maxn = 0, maxninp = 0;
     int device = 0;
     // device buffers
     RegionDev *d_rd = nullptr;
@@ -107,8 +75,6 @@ struct sml_reservoirs {
     uint16_t *d_a_col = nullptr, *d_w_col = nullptr;
     void *d_a_val = nullptr, *d_w_val = nullptr, *d_wout = nullptr;
     // ELL copies (row-major per region), used when rows are short enough
-    std::vector<int> a_ell_cap, w_ell_cap;  // slots per row reserved per region
-    int64_t tot_a_ell = 0, tot_w_ell = 0, tot_a_om = 0, tot_a_oe = 0;
     uint16_t *d_a_ell_col = nullptr, *d_w_ell_col = nullptr;
     void *d_a_ell_val = nullptr, *d_w_ell_val = nullptr;
     uint64_t *d_a_om = nullptr;   // A's overflow bits, one word per 64 rows
@@ -1366,17 +1332,11 @@ int dalloc_bytes(void **p, size_t bytes) {
 
 size_t wbytes(const sml_reservoirs *c) { return c->wdtype == SML_F32 ? 4 : 8; }
 
-// mean/std index (0-based) of output o of the bottom-level 2x2 reservoir:
-// atmo (var,x,y,z) -> (var-1)*8+z, logp -> 33, precip -> 35 (1-based; :1815-1846)
-int out_std_index(int o, const RegionGeom &g) {
-    const int res2d = g.resx * g.resy, natmo = kVars * res2d * kZGrid;
-    if (o < natmo) {
-        const int v = o % kVars, z = o / (kVars * res2d);
-        return v * kZGrid + z;
-    }
-    if (o < natmo + res2d) return 32;
-    if (o < natmo + 2 * res2d) return 34;
-    return -1;
+// the one dispatch on the weights' storage dtype: f(float{}) or f(double{})
+template <typename F>
+auto with_wt(const sml_reservoirs *c, F &&f) {
+    if (c->wdtype == SML_F32) return f(float{});
+    return f(double{});
 }
 
 template <typename T>
@@ -1385,135 +1345,26 @@ int upload(T *dst, const std::vector<T> &src) {
     return SML_OK;
 }
 
+// the exchange / tiling tables (build_region_tables): each allocated, then uploaded
 int build_tables(sml_reservoirs *c) {
-    if (c->generic) {  // no exchange / tiling tables: only the unstandardize slots
-        if (int rc = dalloc(&c->d_outl, c->nout)) return rc;
-        SML_HIP(hipMemcpy(c->d_outl, c->out_l.data(), c->nout, hipMemcpyHostToDevice));
-        return SML_OK;
-    }
-    // assemble: every region of the decomposition (outvec_all is global)
-    std::vector<int32_t> dst((size_t)c->numregions * c->nout, -1);
-    for (int r = 0; r < c->numregions; ++r) {
-        RegionGeom g;
-        region_geom(c->numregions, r, &g);
-        const int rx = g.resx, ry = g.resy, natmo = kVars * rx * ry * kZGrid;
-        for (int o = 0; o < c->nout; ++o) {
-            int d = -1;
-            if (o < natmo) {
-                const int v = o % kVars, x = (o / kVars) % rx, y = (o / (kVars * rx)) % ry, z = o / (kVars * rx * ry);
-                d = g4(v, g.res_xstart - 1 + x, g.res_ystart - 1 + y, z);
-            } else if (o < natmo + rx * ry) {
-                const int p = o - natmo;
-                d = kGrid4d + g2(g.res_xstart - 1 + p % rx, g.res_ystart - 1 + p / rx);
-            } else if (o < natmo + 2 * rx * ry) {
-                const int p = o - natmo - rx * ry;
-                d = kGrid4d + kGrid2d + g2(g.res_xstart - 1 + p % rx, g.res_ystart - 1 + p / rx);
-            }
-            dst[(size_t)r * c->nout + o] = d;
-        }
-    }
-    // feedback tiles of the local regions (tile_4d_and_logp_to_local_state_input +
-    // standardize_state_vec_input + precip standardisation + tisr + sst)
-    std::vector<int32_t> fsrc(c->tot_fb);
-    std::vector<uint8_t> fl(c->tot_fb, 0);
-    std::vector<uint16_t> freg(c->tot_fb);
-    std::vector<int32_t> lsrc((size_t)c->nlocal * std::max(c->ncs, 1), 0);
-    std::vector<uint8_t> ll((size_t)c->nlocal * std::max(c->ncs, 1), 0);
-    std::vector<int32_t> tfb, tgi;
-    std::vector<uint16_t> treg;
-    for (int i = 0; i < c->nlocal; ++i) {
-        const RegionGeom &g = c->geom[i];
-        const int ix = g.inx, iy = g.iny, in2d = ix * iy, natmo = kVars * in2d * kZGrid;
-        const int64_t base = c->rd[i].fb;
-        auto gx = [&](int lx) { return input_x(g, lx + 1) - 1; };
-        for (int z = 0; z < kZGrid; ++z)
-            for (int ly = 0; ly < iy; ++ly)
-                for (int lx = 0; lx < ix; ++lx)
-                    for (int v = 0; v < kVars; ++v) {
-                        const int64_t e = base + v + kVars * (lx + ix * (ly + iy * z));
-                        fsrc[e] = g4(v, gx(lx), g.in_ystart - 1 + ly, z);
-                        fl[e] = (uint8_t)(v * kZGrid + z);
-                    }
-        for (int ly = 0; ly < iy; ++ly)
-            for (int lx = 0; lx < ix; ++lx) {
-                const int p = lx + ix * ly;
-                fsrc[base + natmo + p] = kGrid4d + g2(gx(lx), g.in_ystart - 1 + ly);
-                fl[base + natmo + p] = 32;  // logp (l = 33)
-                fsrc[base + natmo + in2d + p] = kGrid4d + kGrid2d + g2(gx(lx), g.in_ystart - 1 + ly);
-                fl[base + natmo + in2d + p] = 34;  // precip (l = 35)
-            }
-        int64_t off = base + natmo + 2 * in2d;
-        if (c->sst[i]) {
-            for (int p = 0; p < in2d; ++p) fsrc[off + p] = kSrcKeep;
-            off += in2d;
-        }
-        for (int p = 0; p < in2d; ++p) {
-            fsrc[off + p] = -2 - (i * kTisrStride + p);
-            tfb.push_back((int32_t)(off + p));
-            tgi.push_back(g2(gx(p % ix), g.in_ystart - 1 + p / ix));
-            treg.push_back((uint16_t)i);
-        }
-        for (int64_t e = base; e < base + c->ninp[i]; ++e) freg[e] = (uint16_t)i;
-        // local_model: the region's own points of the SPEEDY forecast grids
-        const int rx = g.resx, ry = g.resy, na = kVars * rx * ry * kZGrid;
-        for (int cidx = 0; cidx < c->ncs; ++cidx) {
-            int s = 0, l = 0;
-            if (cidx < na) {
-                const int v = cidx % kVars, x = (cidx / kVars) % rx, y = (cidx / (kVars * rx)) % ry,
-                          z = cidx / (kVars * rx * ry);
-                s = g4(v, g.res_xstart - 1 + x, g.res_ystart - 1 + y, z);
-                l = v * kZGrid + z;
-            } else {
-                const int p = cidx - na;
-                s = kGrid4d + g2(g.res_xstart - 1 + p % rx, g.res_ystart - 1 + (p / rx) % ry);
-                l = 32;
-            }
-            lsrc[(size_t)i * c->ncs + cidx] = s;
-            ll[(size_t)i * c->ncs + cidx] = (uint8_t)l;
-        }
-    }
-    std::vector<int8_t> outl(c->nout);
-    for (int o = 0; o < c->nout; ++o) outl[o] = (int8_t)out_std_index(o, c->geom.empty() ? RegionGeom{} : c->geom[0]);
+    const TablesIn in{c->numregions, c->nlocal, c->ncs, c->nout, c->geom.data(), c->sst.data(), c->ninp.data(),
+                      c->rd.data(), c->tot_fb, c->generic ? c->out_l.data() : nullptr};
+    RegionTables t;
+    if (int rc = build_region_tables(in, &t)) return rc;
+    auto mk = [](auto **d, const auto &v) {
+        const int rc = dalloc(d, v.size());
+        return rc ? rc : upload(*d, v);
+    };
+    if (c->generic) return mk(&c->d_outl, t.outl);
+    c->tot_tisr = (int)t.tisr_fb.size();
     int rc;
-    if ((rc = dalloc(&c->d_asm_dst, dst.size())) || (rc = dalloc(&c->d_fb_src, fsrc.size())) ||
-        (rc = dalloc(&c->d_fb_l, fl.size())) || (rc = dalloc(&c->d_fb_reg, freg.size())) ||
-        (rc = dalloc(&c->d_lm_src, lsrc.size())) || (rc = dalloc(&c->d_lm_l, ll.size())) ||
-        (rc = dalloc(&c->d_outl, outl.size())) || (rc = dalloc(&c->d_tisr_fb, tfb.size())) ||
-        (rc = dalloc(&c->d_tisr_grid, tgi.size())) || (rc = dalloc(&c->d_tisr_reg, treg.size())))
+    if ((rc = mk(&c->d_asm_dst, t.asm_dst)) || (rc = mk(&c->d_fb_src, t.fb_src)) || (rc = mk(&c->d_fb_l, t.fb_l)) ||
+        (rc = mk(&c->d_fb_reg, t.fb_reg)) || (rc = mk(&c->d_lm_src, t.lm_src)) || (rc = mk(&c->d_lm_l, t.lm_l)) ||
+        (rc = mk(&c->d_outl, t.outl)) || (rc = mk(&c->d_tisr_fb, t.tisr_fb)) ||
+        (rc = mk(&c->d_tisr_grid, t.tisr_grid)) || (rc = mk(&c->d_tisr_reg, t.tisr_reg)) ||
+        (rc = mk(&c->d_tgt_idx, t.tgt_idx)))
         return rc;
-    c->tot_tisr = (int)tfb.size();
-    // the training targets' positions in each local region's feedback (the drive's gather)
-    std::vector<int32_t> tidx((size_t)c->nlocal * c->nout, 0);
-    for (int i = 0; i < c->nlocal; ++i) {
-        std::vector<int32_t> t((size_t)(kVars * kZGrid + 2) * c->geom[i].inx * c->geom[i].iny);
-        const int cnt = region_target_index(c->geom[i], t.data());
-        SML_REQUIRE(cnt == c->nout, "region %d: %d training targets, nout %d", i, cnt, c->nout);
-        std::copy(t.begin(), t.begin() + cnt, tidx.begin() + (size_t)i * c->nout);
-    }
-    if ((rc = dalloc(&c->d_tgt_idx, tidx.size())) || (rc = upload(c->d_tgt_idx, tidx))) return rc;
-    if ((rc = upload(c->d_tisr_fb, tfb)) || (rc = upload(c->d_tisr_grid, tgi)) || (rc = upload(c->d_tisr_reg, treg)))
-        return rc;
-    SML_HIP(hipMemcpy(c->d_asm_dst, dst.data(), dst.size() * 4, hipMemcpyHostToDevice));
-    if (!fsrc.empty()) {
-        SML_HIP(hipMemcpy(c->d_fb_src, fsrc.data(), fsrc.size() * 4, hipMemcpyHostToDevice));
-        SML_HIP(hipMemcpy(c->d_fb_l, fl.data(), fl.size(), hipMemcpyHostToDevice));
-        SML_HIP(hipMemcpy(c->d_fb_reg, freg.data(), freg.size() * 2, hipMemcpyHostToDevice));
-    }
-    SML_HIP(hipMemcpy(c->d_lm_src, lsrc.data(), lsrc.size() * 4, hipMemcpyHostToDevice));
-    SML_HIP(hipMemcpy(c->d_lm_l, ll.data(), ll.size(), hipMemcpyHostToDevice));
-    SML_HIP(hipMemcpy(c->d_outl, outl.data(), outl.size(), hipMemcpyHostToDevice));
     return SML_OK;
-}
-
-// convert to the storage dtype; fp32 storage demands exact representability
-template <typename S, typename D>
-bool narrow(const S *src, size_t count, std::vector<D> &out) {
-    out.resize(count);
-    for (size_t i = 0; i < count; ++i) {
-        out[i] = (D)src[i];
-        if ((S)out[i] != src[i] && !(src[i] != src[i])) return false;
-    }
-    return true;
 }
 
 // W_in's CSR pool holds n entries per region at create (the trained W_in has one
@@ -1555,165 +1406,44 @@ int grow_win_pool(sml_reservoirs *c, int i, int64_t wnz) {
     return SML_OK;
 }
 
+// one upload of a region's load: src to byte offset `at` of a pool (nothing for an
+// empty vector: a layout the region does not have; A's CSR entries are copied whatever
+// their count, k = 0 included)
+template <typename T>
+int put(void *pool, size_t at, const std::vector<T> &src, bool always = false) {
+    if (always || !src.empty())
+        SML_HIP(hipMemcpy((char *)pool + at, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice));
+    return SML_OK;
+}
+
+// pack the region on the host (pack_region: every check is made there, so a rejected
+// load changes nothing on the device), then upload what it holds
 template <typename SrcT, typename StoT>
 int load_region_impl(sml_reservoirs *c, int i, const int *rows, const int *cols, const SrcT *vals, const SrcT *win,
                      const SrcT *wout, const double *mean, const double *std) {
-    const int n = c->n[i], k = c->k[i], ninp = c->ninp[i], ld = c->ld[i], ncs = c->ncs, nout = c->nout;
-    const RegionDev &rg = c->rd[i];
-    // --- A: COO (1-based) -> CSR, stable in file order (mklsparse, mod_linalg.f90:10-25)
-    std::vector<int32_t> rp(n + 1, 0);
-    for (int e = 0; e < k; ++e) {
-        SML_REQUIRE(rows[e] >= 1 && rows[e] <= n && cols[e] >= 1 && cols[e] <= n,
-                    "region %d: A entry %d out of range (row %d col %d, n %d)", i, e, rows[e], cols[e], n);
-        rp[rows[e]]++;
-    }
-    for (int r = 0; r < n; ++r) rp[r + 1] += rp[r];
-    std::vector<int32_t> fill(rp.begin(), rp.end() - 1);
-    std::vector<uint16_t> acol(k);
-    std::vector<StoT> aval(k);
-    for (int e = 0; e < k; ++e) {
-        const int p = fill[rows[e] - 1]++;
-        acol[p] = (uint16_t)(cols[e] - 1);
-        aval[p] = (StoT)vals[e];
-        SML_REQUIRE((SrcT)aval[p] == vals[e], "region %d: A value %d not representable in the storage dtype", i, e);
-    }
-    // --- W_in: dense win(n, ninp) column-major -> CSR by row, columns ascending
-    std::vector<int32_t> wrp(n + 1, 0);
-    for (int col = 0; col < ninp; ++col)
-        for (int r = 0; r < n; ++r)
-            if (win[(size_t)col * n + r] != (SrcT)0) wrp[r + 1]++;
-    for (int r = 0; r < n; ++r) wrp[r + 1] += wrp[r];
-    const int64_t wnz = wrp[n];
-    if (wnz > c->w_nz_cap[i])  // a W_in denser than trained (up to the dense n x ninp matmul, :1443)
-        if (int rc = grow_win_pool(c, i, wnz)) return rc;
-    std::vector<int32_t> wfill(wrp.begin(), wrp.end() - 1);
-    std::vector<uint16_t> wcol(wnz);
-    std::vector<StoT> wval(wnz);
-    for (int col = 0; col < ninp; ++col)
-        for (int r = 0; r < n; ++r) {
-            const SrcT v = win[(size_t)col * n + r];
-            if (v == (SrcT)0) continue;
-            const int p = wfill[r]++;
-            wcol[p] = (uint16_t)col;
-            wval[p] = (StoT)v;
-            SML_REQUIRE((SrcT)wval[p] == v, "region %d: W_in value not representable in the storage dtype", i);
-        }
-    // --- W_out: wout(nout, ncs+n) column-major -> [nout_pad][ld] row-major
-    std::vector<StoT> wt((size_t)c->nout_pad * ld, (StoT)0);
-    for (int j = 0; j < ncs + n; ++j)
-        for (int o = 0; o < nout; ++o) {
-            const SrcT v = wout[(size_t)j * nout + o];
-            StoT s = (StoT)v;
-            SML_REQUIRE((SrcT)s == v || v != v, "region %d: W_out value not representable in the storage dtype", i);
-            wt[(size_t)o * ld + j] = s;
-        }
-    // --- upload
+    PackedRegion<StoT> p;
+    const PackIn in{i, c->k[i], c->ncs, c->nout, c->nout_pad, c->a_ell_cap[i], c->w_ell_cap[i]};
+    if (int rc = pack_region(in, c->rd[i], rows, cols, vals, win, wout, &p)) return rc;
+    if (p.wnz > c->w_nz_cap[i])  // a W_in denser than trained (up to the dense n x ninp matmul, :1443)
+        if (int rc = grow_win_pool(c, i, p.wnz)) return rc;
+    RegionDev &rg = c->rd[i];
     const size_t wb = sizeof(StoT);
-    SML_HIP(hipMemcpy(c->d_a_rp + rg.a_rp, rp.data(), rp.size() * 4, hipMemcpyHostToDevice));
-    SML_HIP(hipMemcpy(c->d_a_col + rg.a_nz, acol.data(), acol.size() * 2, hipMemcpyHostToDevice));
-    SML_HIP(hipMemcpy((char *)c->d_a_val + rg.a_nz * wb, aval.data(), aval.size() * wb, hipMemcpyHostToDevice));
-    SML_HIP(hipMemcpy(c->d_w_rp + rg.w_rp, wrp.data(), wrp.size() * 4, hipMemcpyHostToDevice));
-    if (wnz) {
-        SML_HIP(hipMemcpy(c->d_w_col + rg.w_nz, wcol.data(), wcol.size() * 2, hipMemcpyHostToDevice));
-        SML_HIP(hipMemcpy((char *)c->d_w_val + rg.w_nz * wb, wval.data(), wval.size() * wb, hipMemcpyHostToDevice));
-    }
-    SML_HIP(hipMemcpy((char *)c->d_wout + rg.wout * wb, wt.data(), wt.size() * wb, hipMemcpyHostToDevice));
-    if (ncs > 0) {  // W_out(:, 1:ncs) as [ncs][nout_pad]: the file's own order (outputs fastest), padded
-        std::vector<StoT> wl((size_t)ncs * c->nout_pad, (StoT)0);
-        for (int j = 0; j < ncs; ++j)
-            for (int o = 0; o < nout; ++o) wl[(size_t)j * c->nout_pad + o] = (StoT)wout[(size_t)j * nout + o];
-        SML_HIP(hipMemcpy((char *)c->d_wlm + rg.wlm * wb, wl.data(), wl.size() * wb, hipMemcpyHostToDevice));
-    }
-    // --- ELL copies (RegionDev): A pair-major with the main width that moves the fewest
-    // bytes, W_in one slot per row -- file order within a row, zero-padded after the
-    // row's entries; a region whose rows do not fit keeps the CSR copies only
-    RegionDev &rgm = c->rd[i];
-    rgm.a_w = rgm.w_w = rgm.a_ov = rgm.w_q = 0;
-    rgm.w_magic = 0;
-    if (c->a_ell_cap[i] > 0) {
-        int maxlen = 0, nmax = 0;
-        for (int r = 0; r < n; ++r) maxlen = std::max(maxlen, rp[r + 1] - rp[r]);
-        for (int r = 0; r < n; ++r) nmax += (rp[r + 1] - rp[r]) == maxlen;
-        if (maxlen >= 1 && maxlen <= c->a_ell_cap[i]) {
-            // bytes per row: the pairs (odd widths padded), + for an overflow list its bit
-            // words / counts (12 B per 64 rows) and an entry per row of maxlen entries
-            const double eb = 2.0 + (double)wb;
-            auto cost = [&](int w, bool ov) {
-                return 2 * ((w + 1) / 2) * eb * n + (ov ? 12.0 * ((n + 63) / 64) + eb * nmax : 0.0);
-            };
-            int w = maxlen;
-            bool ov = false;
-            if (maxlen >= 2 && cost(maxlen - 1, true) < cost(maxlen, false)) {
-                w = maxlen - 1;
-                ov = true;
-            }
-            const int np = (w + 1) / 2;
-            std::vector<uint16_t> ec((size_t)2 * np * n, 0);
-            std::vector<StoT> ev((size_t)2 * np * n, (StoT)0);
-            const int nw = (n + 63) / 64;
-            std::vector<uint64_t> om(ov ? nw : 0, 0ull);
-            std::vector<uint32_t> ob(ov ? nw : 0, 0u);
-            std::vector<uint16_t> oc;
-            std::vector<StoT> ovv;
-            for (int r = 0; r < n; ++r) {
-                if (ov && (r & 63) == 0) ob[r >> 6] = (uint32_t)oc.size();
-                for (int e = rp[r]; e < rp[r + 1]; ++e) {
-                    const int s = e - rp[r];
-                    if (s < w) {  // pair s / 2, half s % 2 of row r
-                        const size_t at = (size_t)(s >> 1) * 2 * n + 2 * (size_t)r + (s & 1);
-                        ec[at] = acol[e];
-                        ev[at] = aval[e];
-                    } else {  // s == w: the overflow entry
-                        om[r >> 6] |= 1ull << (r & 63);
-                        oc.push_back(acol[e]);
-                        ovv.push_back(aval[e]);
-                    }
-                }
-            }
-            SML_HIP(hipMemcpy(c->d_a_ell_col + rgm.a_ell, ec.data(), ec.size() * 2, hipMemcpyHostToDevice));
-            SML_HIP(hipMemcpy((char *)c->d_a_ell_val + rgm.a_ell * wb, ev.data(), ev.size() * wb,
-                              hipMemcpyHostToDevice));
-            if (ov) {
-                SML_HIP(hipMemcpy(c->d_a_om + rgm.a_om, om.data(), om.size() * 8, hipMemcpyHostToDevice));
-                SML_HIP(hipMemcpy(c->d_a_ob + rgm.a_om, ob.data(), ob.size() * 4, hipMemcpyHostToDevice));
-                if (!oc.empty()) {
-                    SML_HIP(hipMemcpy(c->d_a_oc + rgm.a_oe, oc.data(), oc.size() * 2, hipMemcpyHostToDevice));
-                    SML_HIP(hipMemcpy((char *)c->d_a_ov + rgm.a_oe * wb, ovv.data(), ovv.size() * wb,
-                                      hipMemcpyHostToDevice));
-                }
-            }
-            rgm.a_w = w;
-            rgm.a_ov = ov ? 1 : 0;
-        }
-    }
-    if (c->w_ell_cap[i] > 0) {
-        bool one = true;  // exactly one entry per row (train_reservoir's W_in, mod_reservoir.f90:260-278)
-        for (int r = 0; r < n && one; ++r) one = wrp[r + 1] - wrp[r] == 1;
-        if (one) {
-            std::vector<uint16_t> ec(n);
-            std::vector<StoT> ev(n);
-            for (int r = 0; r < n; ++r) {
-                ec[r] = wcol[wrp[r]];
-                ev[r] = wval[wrp[r]];
-            }
-            // block-diagonal (rows (j-1) q + 1 .. j q read input j, q = n / ninp): the
-            // column is i / q, computed as umulhi(i, magic), so only the value is read
-            const int q = ninp > 0 && n % ninp == 0 ? n / ninp : 0;
-            bool implicit = q > 0;
-            const uint32_t magic = q > 0 ? (uint32_t)((0x100000000ull + q - 1) / q) : 0u;
-            for (int r = 0; r < n && implicit; ++r)
-                implicit = ec[r] == r / q && (uint32_t)(((uint64_t)r * magic) >> 32) == (uint32_t)(r / q);
-            SML_HIP(hipMemcpy(c->d_w_ell_col + rgm.w_ell, ec.data(), ec.size() * 2, hipMemcpyHostToDevice));
-            SML_HIP(hipMemcpy((char *)c->d_w_ell_val + rgm.w_ell * wb, ev.data(), ev.size() * wb,
-                              hipMemcpyHostToDevice));
-            rgm.w_w = 1;
-            if (implicit) {
-                rgm.w_q = q;
-                rgm.w_magic = magic;
-            }
-        }
-    }
-    SML_HIP(hipMemcpy(c->d_rd + i, &rgm, sizeof(RegionDev), hipMemcpyHostToDevice));
+    int rc;
+    if ((rc = put(c->d_a_rp, rg.a_rp * 4, p.rp)) || (rc = put(c->d_a_col, rg.a_nz * 2, p.acol, true)) ||
+        (rc = put(c->d_a_val, rg.a_nz * wb, p.aval, true)) || (rc = put(c->d_w_rp, rg.w_rp * 4, p.wrp)) ||
+        (rc = put(c->d_w_col, rg.w_nz * 2, p.wcol)) || (rc = put(c->d_w_val, rg.w_nz * wb, p.wval)) ||
+        (rc = put(c->d_wout, rg.wout * wb, p.wt)) || (rc = put(c->d_wlm, rg.wlm * wb, p.wl)) ||
+        (rc = put(c->d_a_ell_col, rg.a_ell * 2, p.a_ec)) || (rc = put(c->d_a_ell_val, rg.a_ell * wb, p.a_ev)) ||
+        (rc = put(c->d_a_om, rg.a_om * 8, p.om)) || (rc = put(c->d_a_ob, rg.a_om * 4, p.ob)) ||
+        (rc = put(c->d_a_oc, rg.a_oe * 2, p.oc)) || (rc = put(c->d_a_ov, rg.a_oe * wb, p.ovv)) ||
+        (rc = put(c->d_w_ell_col, rg.w_ell * 2, p.w_ec)) || (rc = put(c->d_w_ell_val, rg.w_ell * wb, p.w_ev)))
+        return rc;
+    rg.a_w = p.a_w;
+    rg.a_ov = p.a_ov;
+    rg.w_w = p.w_w;
+    rg.w_q = p.w_q;
+    rg.w_magic = p.w_magic;
+    SML_HIP(hipMemcpy(c->d_rd + i, &rg, sizeof(RegionDev), hipMemcpyHostToDevice));
     c->ell_ok = -1;
     double ms[2 * kMeanStd];
     std::memcpy(ms, mean, sizeof(double) * kMeanStd);
@@ -1817,9 +1547,7 @@ int res_create_impl(int numregions, int nlocal, const int *region_ids, const uns
     c->meanstd_h.assign((size_t)nlocal * 2 * kMeanStd, 0.0);
     c->geom.resize(nlocal);
     c->ninp.resize(nlocal);
-    c->ld.resize(nlocal);
-    c->rd.resize(nlocal);
-    c->w_nz_cap.resize(nlocal);
+    // --- validate
     for (int i = 0; i < nlocal; ++i) {
         if (!region_geom(numregions, region_ids[i], &c->geom[i])) {
             sml_res_destroy(c);
@@ -1841,52 +1569,11 @@ int res_create_impl(int numregions, int nlocal, const int *region_ids, const uns
             sml_res_destroy(c);
             return fail(SML_ERR_ARG, "region %d: ninp %d (1..65535)", i, c->ninp[i]);
         }
-        // W_out rows (and x_aug) padded to 32 columns: with the streamed columns starting
-        // at ncs & ~31, every 1 KB load of a wave is whole 128-B lines (no line fetched
-        // by two neighbouring loads)
-        c->ld[i] = (chunk_speedy + n[i] + kLdAlign - 1) / kLdAlign * kLdAlign;
-        c->w_nz_cap[i] = n[i];
-        RegionDev &r = c->rd[i];
-        r.n = n[i];
-        r.ninp = c->ninp[i];
-        r.ld = c->ld[i];
-        r.a_rp = c->tot_a_rp;
-        c->tot_a_rp += n[i] + 1;
-        r.a_nz = c->tot_a_nz;
-        c->tot_a_nz += k[i];
-        r.w_rp = c->tot_w_rp;
-        c->tot_w_rp += n[i] + 1;
-        r.w_nz = c->tot_w_nz;
-        c->tot_w_nz += n[i];
-        r.wout = c->tot_wout;
-        c->tot_wout += (int64_t)c->nout_pad * c->ld[i];
-        r.wlm = c->tot_wlm;
-        c->tot_wlm += (int64_t)c->ncs * c->nout_pad;
-        // the state's slot is the x~ column block of the region's ld-wide row (column
-        // ncs on, 32-column aligned start, zero padding after n): the readout streams
-        // x~ straight from the state the update wrote, squaring the even-numbered
-        // entries as it loads them, so the update writes 8 B per row less
-        r.xaug = c->tot_xaug;
-        c->tot_xaug += c->ld[i];
-        r.x = r.xaug + chunk_speedy;
-        r.fb = c->tot_fb;
-        c->tot_fb += c->ninp[i];
-        c->maxn = std::max(c->maxn, n[i]);
-        c->maxninp = std::max(c->maxninp, c->ninp[i]);
-        // makesparse rows hold floor(k/n) or floor(k/n)+1 entries (per-block permutations)
-        c->a_ell_cap.push_back(!c->no_ell && k[i] / n[i] + 1 <= kEllA ? kEllA : 0);
-        c->w_ell_cap.push_back(c->no_ell ? 0 : kEllW);
-        r.a_w = r.w_w = r.a_ov = r.w_q = 0;
-        r.w_magic = 0;
-        r.a_ell = c->tot_a_ell;
-        c->tot_a_ell += (int64_t)c->a_ell_cap.back() * n[i];
-        r.w_ell = c->tot_w_ell;
-        c->tot_w_ell += (int64_t)c->w_ell_cap.back() * n[i];
-        r.a_om = c->tot_a_om;
-        c->tot_a_om += c->a_ell_cap.back() ? (n[i] + 63) / 64 : 0;
-        r.a_oe = c->tot_a_oe;
-        c->tot_a_oe += c->a_ell_cap.back() ? n[i] : 0;
     }
+    // --- plan: every region's offsets into the pools, the pools' sizes
+    static_cast<PoolPlan &>(*c) = plan_pools({nlocal, n, k, c->ninp.data(), chunk_speedy, c->nout_pad, c->no_ell});
+    c->w_nz_cap.assign(n, n + nlocal);
+    // --- allocate
     const size_t wb = wbytes(c);
     int rc;
     if ((rc = dalloc(&c->d_a_ell_col, std::max<int64_t>(c->tot_a_ell, 1))) ||
@@ -1912,6 +1599,7 @@ int res_create_impl(int numregions, int nlocal, const int *region_ids, const uns
         sml_res_destroy(c);
         return rc;
     }
+    // --- clear, upload
     hipError_t e = hipSuccess;
     if (e == hipSuccess) e = hipMemset(c->d_zero, 0, 256);
     if (e == hipSuccess) e = hipMemset(c->d_a_rp, 0, std::max<int64_t>(c->tot_a_rp, 1) * 4);
@@ -1999,8 +1687,9 @@ extern "C" int sml_res_load_region_f32(sml_reservoirs *c, int i, const int *rows
                                        const float *win, const float *wout, const double *mean, const double *std) {
     if (int rc = check_region(c, i)) return rc;
     SML_REQUIRE(win && wout && mean && std && (c->k[i] == 0 || (rows && cols && vals)), "null weight array");
-    if (c->wdtype == SML_F32) return load_region_impl<float, float>(c, i, rows, cols, vals, win, wout, mean, std);
-    return load_region_impl<float, double>(c, i, rows, cols, vals, win, wout, mean, std);
+    return with_wt(c, [&](auto tag) {
+        return load_region_impl<float, decltype(tag)>(c, i, rows, cols, vals, win, wout, mean, std);
+    });
 }
 
 extern "C" int sml_res_load_region_f64(sml_reservoirs *c, int i, const int *rows, const int *cols,
@@ -2008,8 +1697,9 @@ extern "C" int sml_res_load_region_f64(sml_reservoirs *c, int i, const int *rows
                                        const double *mean, const double *std) {
     if (int rc = check_region(c, i)) return rc;
     SML_REQUIRE(win && wout && mean && std && (c->k[i] == 0 || (rows && cols && vals)), "null weight array");
-    if (c->wdtype == SML_F32) return load_region_impl<double, float>(c, i, rows, cols, vals, win, wout, mean, std);
-    return load_region_impl<double, double>(c, i, rows, cols, vals, win, wout, mean, std);
+    return with_wt(c, [&](auto tag) {
+        return load_region_impl<double, decltype(tag)>(c, i, rows, cols, vals, win, wout, mean, std);
+    });
 }
 
 extern "C" int sml_res_set_state(sml_reservoirs *c, int i, const double *x) {
@@ -2078,8 +1768,8 @@ extern "C" int sml_res_set_reference_paths(sml_reservoirs *c, int flags) {
         // (the ELL buffers stay sized for the default: a region is laid out in ELL only
         // while its cap is non-zero, at load)
         for (int i = 0; i < c->nlocal; ++i) {
-            c->a_ell_cap[i] = !csr && c->k[i] / c->n[i] + 1 <= kEllA ? kEllA : 0;
-            c->w_ell_cap[i] = csr ? 0 : kEllW;
+            c->a_ell_cap[i] = ell_cap_a(c->n[i], c->k[i], csr);
+            c->w_ell_cap[i] = ell_cap_w(csr);
         }
         c->ell_ok = -1;
     }
@@ -2179,13 +1869,8 @@ int launch_update_bal(sml_reservoirs *c, const double *xo, double *xn, const dou
         c->blk_cap = cap;
     }
     if (c->blk_off[G] < 0) {  // each block's first region, for this grid: once per G
-        std::vector<int32_t> r0(G);
-        for (int b = 0; b < G; ++b) {
-            const int64_t g0 = total * b / G;
-            r0[b] = (int32_t)(std::upper_bound(c->row0_h.begin(), c->row0_h.end(), (int32_t)g0) - c->row0_h.begin() - 1);
-        }
         c->blk_off[G] = G * (G - 1) / 2;
-        c->blk_host.push_back(std::move(r0));  // ordered before the launch on st
+        c->blk_host.push_back(block_first_regions(c->row0_h, G));  // ordered before the launch on st
         SML_HIP(hipMemcpyAsync(c->d_blk_r0 + c->blk_off[G], c->blk_host.back().data(), (size_t)G * 4,
                                hipMemcpyHostToDevice, st));
     }
@@ -2206,17 +1891,12 @@ int launch_update_bal(sml_reservoirs *c, const double *xo, double *xn, const dou
                            total, ell, xo, xn, d_feedback, c->leakage, lds_x, lds_buf);
     };
     // two passes of A / W_in rows in flight (a third measured slower: 114-124 VGPRs)
-#define SML_BAL(WT)                                                                                         \
-    do {                                                                                                    \
-        if (np == 2) ovf ? go(k_res_update_bal<WT, 2, true, 2>) : go(k_res_update_bal<WT, 2, false, 2>);    \
-        else if (np == 3) ovf ? go(k_res_update_bal<WT, 3, true, 2>) : go(k_res_update_bal<WT, 3, false, 2>); \
-        else ovf ? go(k_res_update_bal<WT, 4, true, 2>) : go(k_res_update_bal<WT, 4, false, 2>);             \
-    } while (0)
-    if (c->wdtype == SML_F32)
-        SML_BAL(float);
-    else
-        SML_BAL(double);
-#undef SML_BAL
+    with_wt(c, [&](auto tag) {
+        using WT = decltype(tag);
+        if (np == 2) ovf ? go(k_res_update_bal<WT, 2, true, 2>) : go(k_res_update_bal<WT, 2, false, 2>);
+        else if (np == 3) ovf ? go(k_res_update_bal<WT, 3, true, 2>) : go(k_res_update_bal<WT, 3, false, 2>);
+        else ovf ? go(k_res_update_bal<WT, 4, true, 2>) : go(k_res_update_bal<WT, 4, false, 2>);
+    });
     SML_HIP(hipGetLastError());
     return SML_OK;
 }
@@ -2235,23 +1915,17 @@ int launch_update(sml_reservoirs *c, const double *xo, double *xn, const double 
     const int bpr = parts;
     const int nlog = bpr * c->nlocal;
     const dim3 ug(nlog);
-#define SML_UPD(WT, L)                                                                                            \
-    hipLaunchKernelGGL((k_res_update<WT, L, 4>), ug, dim3(kUpdThreads),                                          \
-                       L ? lds : 0, st, c->d_rd, c->d_a_rp, c->d_a_col, (const WT *)c->d_a_val, c->d_w_rp,        \
-                       c->d_w_col, (const WT *)c->d_w_val, ell, xo, xn, d_feedback, c->leakage, bpr, lds_x, nlog)
     const Ell ell = make_ell(c);
-    if (c->wdtype == SML_F32) {
-        if (use_lds)
-            SML_UPD(float, true);
-        else
-            SML_UPD(float, false);
-    } else {
-        if (use_lds)
-            SML_UPD(double, true);
-        else
-            SML_UPD(double, false);
-    }
-#undef SML_UPD
+    with_wt(c, [&](auto tag) {
+        using WT = decltype(tag);
+        auto go = [&](auto kern, size_t shared) {
+            hipLaunchKernelGGL(kern, ug, dim3(kUpdThreads), shared, st, c->d_rd, c->d_a_rp, c->d_a_col,
+                               (const WT *)c->d_a_val, c->d_w_rp, c->d_w_col, (const WT *)c->d_w_val, ell, xo, xn,
+                               d_feedback, c->leakage, bpr, lds_x, nlog);
+        };
+        if (use_lds) go(k_res_update<WT, true, 4>, lds);
+        else go(k_res_update<WT, false, 4>, 0);
+    });
     SML_HIP(hipGetLastError());
     return SML_OK;
 }
@@ -2271,21 +1945,18 @@ int launch_begin(sml_reservoirs *c, const double *xo, double *xn, const double *
     const size_t lds = (size_t)(lds_x + c->maxninp) * sizeof(double);
     const int groups = c->nout_pad / kRowsWide;
     const Ell ell = make_ell(c);
-    auto go = [&](auto wt_tag, auto kern) {
-        using WT = decltype(wt_tag);
-        hipLaunchKernelGGL(kern, dim3(c->nlocal), dim3(kBeginThreads), lds, st, c->d_rd, c->d_a_rp, c->d_a_col,
-                           (const WT *)c->d_a_val, c->d_w_rp, c->d_w_col, (const WT *)c->d_w_val, ell, xo, xn,
-                           d_feedback, c->ncs, c->leakage, lds_x, (const WT *)c->d_wout, c->d_part,
-                           c->nout_pad, groups);
-    };
     const bool two = begin_mode(c) == 2;
-    if (c->wdtype == SML_F32) {
-        if (two) go(float{}, k_res_begin<float, 2, 2>);
-        else go(float{}, k_res_begin<float, 1, 4>);
-    } else {
-        if (two) go(double{}, k_res_begin<double, 2, 2>);
-        else go(double{}, k_res_begin<double, 1, 4>);
-    }
+    with_wt(c, [&](auto tag) {
+        using WT = decltype(tag);
+        auto go = [&](auto kern) {
+            hipLaunchKernelGGL(kern, dim3(c->nlocal), dim3(kBeginThreads), lds, st, c->d_rd, c->d_a_rp, c->d_a_col,
+                               (const WT *)c->d_a_val, c->d_w_rp, c->d_w_col, (const WT *)c->d_w_val, ell, xo, xn,
+                               d_feedback, c->ncs, c->leakage, lds_x, (const WT *)c->d_wout, c->d_part,
+                               c->nout_pad, groups);
+        };
+        if (two) go(k_res_begin<WT, 2, 2>);
+        else go(k_res_begin<WT, 1, 4>);
+    });
     SML_HIP(hipGetLastError());
     return SML_OK;
 }
@@ -2303,14 +1974,12 @@ void launch_readout(sml_reservoirs *c, const double *xs, const double *d_local_m
                     hipStream_t st, double *d_raw = nullptr) {
     if constexpr (kMode == kReadFinish) {
         const int total = c->nlocal * c->nout_pad;
-        if (c->wdtype == SML_F32)
-            hipLaunchKernelGGL(k_res_finish<float>, dim3((total + 255) / 256), dim3(256), 0, st, c->d_rd,
-                               (const float *)c->d_wlm, d_local_model, c->d_meanstd, c->d_outl, c->d_part, d_outvec,
+        with_wt(c, [&](auto tag) {
+            using WT = decltype(tag);
+            hipLaunchKernelGGL(k_res_finish<WT>, dim3((total + 255) / 256), dim3(256), 0, st, c->d_rd,
+                               (const WT *)c->d_wlm, d_local_model, c->d_meanstd, c->d_outl, c->d_part, d_outvec,
                                c->nout, c->ov_ld, c->nout_pad, c->ncs, c->nlocal, d_raw);
-        else
-            hipLaunchKernelGGL(k_res_finish<double>, dim3((total + 255) / 256), dim3(256), 0, st, c->d_rd,
-                               (const double *)c->d_wlm, d_local_model, c->d_meanstd, c->d_outl, c->d_part,
-                               d_outvec, c->nout, c->ov_ld, c->nout_pad, c->ncs, c->nlocal, d_raw);
+        });
     } else {
         const bool wide = c->nout_pad % kRowsWide == 0 && c->nout_pad / kRowsWide <= 8;
         const int rows = wide ? kRowsWide : kRows;
@@ -2324,22 +1993,16 @@ void launch_readout(sml_reservoirs *c, const double *xs, const double *d_local_m
             ipw = (nitems + c->read_waves - 1) / c->read_waves;
         const int nwaves = (nitems + ipw - 1) / ipw;
         const int nblocks = (nwaves + wpb - 1) / wpb;
-        auto go = [&](auto wt_tag, auto r_tag) {
-            using WT = decltype(wt_tag);
-            constexpr int R = decltype(r_tag)::value;
-            hipLaunchKernelGGL((k_res_readout<WT, kMode, R>), dim3(nblocks), dim3(64 * wpb), 0, st, c->d_rd,
-                               (const WT *)c->d_wout, (const WT *)c->d_wlm, xs, d_local_model, c->d_meanstd,
-                               c->d_outl, c->d_part, d_outvec, c->nout, c->ov_ld, c->nout_pad, c->ncs, groups, nitems, ipw);
-        };
-        using RW = std::integral_constant<int, kRowsWide>;
-        using RN = std::integral_constant<int, kRows>;
-        if (c->wdtype == SML_F32) {
-            if (wide) go(float{}, RW{});
-            else go(float{}, RN{});
-        } else {
-            if (wide) go(double{}, RW{});
-            else go(double{}, RN{});
-        }
+        with_wt(c, [&](auto tag) {
+            using WT = decltype(tag);
+            auto go = [&](auto kern) {
+                hipLaunchKernelGGL(kern, dim3(nblocks), dim3(64 * wpb), 0, st, c->d_rd, (const WT *)c->d_wout,
+                                   (const WT *)c->d_wlm, xs, d_local_model, c->d_meanstd, c->d_outl, c->d_part,
+                                   d_outvec, c->nout, c->ov_ld, c->nout_pad, c->ncs, groups, nitems, ipw);
+            };
+            if (wide) go(k_res_readout<WT, kMode, kRowsWide>);
+            else go(k_res_readout<WT, kMode, kRows>);
+        });
     }
 }
 }  // namespace
@@ -2435,23 +2098,17 @@ void launch_finish_grid(sml_reservoirs *c, const double *d_fc4d, const double *d
                         double *d_outvec, double *d_grid4d, double *d_grid2d, double *d_precip, hipStream_t st) {
     const bool grouped = c->ncs > 0 && c->nout_pad % 4 == 0 && c->nout_pad <= 144 && c->nout_pad / 4 * kFinGroups <= 256 &&
                          (c->ncs + kFinGroups - 1) / kFinGroups <= kFinGsz && !c->finish_ungrouped;
-    auto go = [&](auto wt_tag, auto grouped_tag) {
-        using WT = decltype(wt_tag);
-        hipLaunchKernelGGL((k_res_finish_grid<WT, kAsm, decltype(grouped_tag)::value>), dim3(c->nlocal), dim3(256), 0,
-                           st, c->d_rd, (const WT *)c->d_wlm, c->d_lm_src, c->d_lm_l, d_fc4d, d_fc2d, d_local_model,
-                           c->d_meanstd, c->d_outl, c->d_part, d_outvec, c->nout, c->ov_ld, c->nout_pad, c->ncs,
-                           c->d_asm_dst, d_grid4d, d_grid2d, d_precip, c->fin_wflag, c->fin_wval, c->fin_wlate,
-                           c->fin_wtimeout);
-    };
-    using G1 = std::integral_constant<bool, true>;
-    using G0 = std::integral_constant<bool, false>;
-    if (c->wdtype == SML_F32) {
-        if (grouped) go(float{}, G1{});
-        else go(float{}, G0{});
-    } else {
-        if (grouped) go(double{}, G1{});
-        else go(double{}, G0{});
-    }
+    with_wt(c, [&](auto tag) {
+        using WT = decltype(tag);
+        auto go = [&](auto kern) {
+            hipLaunchKernelGGL(kern, dim3(c->nlocal), dim3(256), 0, st, c->d_rd, (const WT *)c->d_wlm, c->d_lm_src,
+                               c->d_lm_l, d_fc4d, d_fc2d, d_local_model, c->d_meanstd, c->d_outl, c->d_part, d_outvec,
+                               c->nout, c->ov_ld, c->nout_pad, c->ncs, c->d_asm_dst, d_grid4d, d_grid2d, d_precip,
+                               c->fin_wflag, c->fin_wval, c->fin_wlate, c->fin_wtimeout);
+        };
+        if (grouped) go(k_res_finish_grid<WT, kAsm, true>);
+        else go(k_res_finish_grid<WT, kAsm, false>);
+    });
     c->fin_wflag = nullptr;  // one launch
     c->fin_wlate = nullptr;
 }
@@ -2594,18 +2251,14 @@ extern "C" int sml_res_train_drive(sml_reservoirs *c, const double *d_inputs, in
     }
     const int lds_x = (c->maxn + 1) / 2 * 2;
     const Ell ell = make_ell(c);
-    auto go = [&](auto wt_tag) {
-        using WT = decltype(wt_tag);
+    with_wt(c, [&](auto tag) {
+        using WT = decltype(tag);
         hipLaunchKernelGGL(k_res_drive<WT>, dim3(c->nlocal), dim3(kUpdThreads), lds, st, c->d_rd, c->d_row0,
                            c->d_a_rp, c->d_a_col, (const WT *)c->d_a_val, c->d_w_rp, c->d_w_col,
                            (const WT *)c->d_w_val, ell, c->d_x[c->cur], c->d_x[1 - c->cur], d_inputs, stride, d_model,
                            model_stride, c->d_tgt_idx, d_states, d_targets, m, c->ncs, c->nout, c->leakage, lds_x,
                            c->maxninp);
-    };
-    if (c->wdtype == SML_F32)
-        go(float{});
-    else
-        go(double{});
+    });
     SML_HIP(hipGetLastError());
     c->cur = 1 - c->cur;
     return SML_OK;
@@ -2624,10 +2277,9 @@ extern "C" int sml_res_spectral_radius(sml_reservoirs *c, double tol, int max_it
     // x and y of a region in LDS where they fit (and the scratch is not forced); the
     // kernel keeps no static LDS, but what the compiler reports is taken off the limit
     hipFuncAttributes fa;
-    if (c->wdtype == SML_F32)
-        SML_HIP(hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(&k_res_radius<float>)));
-    else
-        SML_HIP(hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(&k_res_radius<double>)));
+    SML_HIP(with_wt(c, [&](auto tag) {
+        return hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(&k_res_radius<decltype(tag)>));
+    }));
     const size_t lds_limit = c->radius_global || fa.sharedSizeBytes > c->max_lds ? 0 : c->max_lds - fa.sharedSizeBytes;
     size_t lds = 0;
     bool scratch = false;
@@ -2645,16 +2297,12 @@ extern "C" int sml_res_spectral_radius(sml_reservoirs *c, double tol, int max_it
     if (scratch && !c->d_rad_xy)
         if (int rc = dalloc(&c->d_rad_xy, 2 * (size_t)c->row0_h[c->nlocal])) return rc;
     hipStream_t st = (hipStream_t)stream;
-    auto go = [&](auto wt_tag) {
-        using WT = decltype(wt_tag);
+    with_wt(c, [&](auto tag) {
+        using WT = decltype(tag);
         hipLaunchKernelGGL(k_res_radius<WT>, dim3(c->nlocal), dim3(kUpdThreads), lds, st, c->d_rd, c->d_row0,
                            c->d_a_rp, c->d_a_col, (const WT *)c->d_a_val, c->d_rad_xy, c->d_rad_part,
                            (RadiusOut *)c->d_rad_out, tol, max_iter, lds_limit);
-    };
-    if (c->wdtype == SML_F32)
-        go(float{});
-    else
-        go(double{});
+    });
     SML_HIP(hipGetLastError());
     SML_HIP(hipStreamSynchronize(st));
     std::vector<RadiusOut> out(c->nlocal);
@@ -2703,19 +2351,8 @@ extern "C" int sml_res_step_host(sml_reservoirs *c, const double *feedback, cons
 
 extern "C" int sml_res_footprint(const sml_reservoirs *c, int64_t *weight_bytes, int64_t *algo_bytes) {
     SML_REQUIRE(c, "null context");
-    const int64_t wb = (int64_t)wbytes(c);
-    int64_t w = 0, a = 0;
-    for (int i = 0; i < c->nlocal; ++i) {
-        const int64_t n = c->n[i], k = c->k[i], ninp = c->ninp[i];
-        const int64_t wout = wb * c->nout * (c->ncs + n);     // unpadded W_out
-        const int64_t amat = 4 * (n + 1) + (2 + wb) * k;      // CSR row ptr + col + val
-        const int64_t winm = 4 * (n + 1) + (2 + wb) * n;      // CSR, one entry per row
-        w += wout + amat + winm;
-        // minimal traffic: weights once, state in + out, feedback, local model, outvec
-        a += wout + amat + winm + 8 * n + 8 * n + 8 * ninp + 8 * c->ncs + 8 * c->nout;
-    }
-    if (weight_bytes) *weight_bytes = w;
-    if (algo_bytes) *algo_bytes = a;
+    footprint(c->nlocal, c->n.data(), c->k.data(), c->ninp.data(), c->ncs, c->nout, (int64_t)wbytes(c), weight_bytes,
+              algo_bytes);
     return SML_OK;
 }
 

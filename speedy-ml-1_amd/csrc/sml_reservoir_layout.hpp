@@ -1,0 +1,145 @@
+// sml_reservoir_layout.hpp -- the reservoir context's weight layout and index tables:
+// what sml_reservoir.hip uploads, computed on the host with no HIP call in between, so
+// the index arithmetic runs (and is sanitised) on a CPU: tests/reservoir_layout_check.cpp.
+#pragma once
+
+#include <cstdint>
+#include <vector>
+
+#include "sml_internal.hpp"
+
+namespace sml {
+
+constexpr int kLdAlign = 32;    // W_out / x_aug row stride multiple (columns)
+constexpr int kRows = 8;        // W_out rows per wave in the readout (nout_pad's multiple)
+constexpr int kMeanStd = 36;    // mean/std vector length (mod_reservoir.f90:1815-1846)
+constexpr int kTisrStride = 16; // packed tisr input: [nlocal][16]
+constexpr int kSrcKeep = -1;    // feedback entry left untouched (sst)
+
+constexpr int kEllA = 8;  // ELL slots reserved per row for A (makesparse rows hold floor(k/n) or +1 <= 8)
+constexpr int kEllW = 1;  // ELL slots per row for W_in (the trained W_in has one entry per row)
+
+// A's ELL copy (r04b): a_w "main" slots per row, stored as slot pairs, pair-major
+// ([pair][n] of (col, col) u16 pairs and of (val, val) pairs: lane i's row is one
+// 4-B + one 8-B load per pair, coalesced across the wave), a_w chosen per region to
+// move the fewest bytes.  makesparse rows hold floor(k/n) or floor(k/n) + 1 entries
+// (mod_linalg.f90:180-218): with a_ov the rows holding a_w + 1 keep their last entry
+// in an overflow list instead of padding every row to the longest -- a bit per row
+// (u64 words) + a count per word locate it.  The dominant 4x4+sst region (n 6048,
+// 4.8 % of rows one longer) moves 36.5 B of A per row instead of 48.
+struct RegionDev {
+    int n, ninp, ld;
+    int a_w, w_w;  // A's ELL main width in slots (0 = use the CSR copy); W_in ELL (1) or CSR (0)
+    int a_ov;      // 1: rows of a_w + 1 entries, the last in the overflow list
+    int w_q;       // > 0: W_in's column of row i is i / w_q = umulhi(i, w_magic), not stored
+    uint32_t w_magic;
+    int64_t a_rp, a_nz, w_rp, w_nz, wout, x, xaug, fb;
+    int64_t wlm;  // W_out(:, 1:ncs) transposed, [ncs][nout_pad], in the W_out pool after the row-major blocks
+    int64_t a_ell, w_ell;  // offsets into the ELL pools (A: pair-major as above; W_in: [n])
+    int64_t a_om;          // overflow bit words / per-word counts: [ceil(n / 64)] each
+    int64_t a_oe;          // overflow entries (col, val) in row order: [n] reserved
+};
+
+// ELL slots per row reserved for region (n, k): makesparse rows hold floor(k/n) or
+// floor(k/n)+1 entries (per-block permutations); none in a CSR-only context
+inline int ell_cap_a(int n, int k, bool csr_only) { return !csr_only && k / n + 1 <= kEllA ? kEllA : 0; }
+inline int ell_cap_w(bool csr_only) { return csr_only ? 0 : kEllW; }
+
+// W_in's implicit block-diagonal column: i / q == umulhi(i, win_magic(q)) for the rows i
+// pack_region verifies (every i < n <= 65535)
+inline uint32_t win_magic(int q) { return (uint32_t)((0x100000000ull + q - 1) / q); }
+
+// ------------------------------------------------------------------ pool planning
+struct PoolPlanIn {
+    int nlocal;
+    const int *n, *k, *ninp;
+    int ncs, nout_pad;
+    bool csr_only;
+};
+
+// every region's offsets into the context's pools (elements of the pool's type), and the
+// pools' sizes
+struct PoolPlan {
+    std::vector<RegionDev> rd;
+    std::vector<int> ld;
+    std::vector<int> a_ell_cap, w_ell_cap;  // ELL slots per row reserved per region
+    int64_t tot_a_rp = 0, tot_a_nz = 0, tot_w_rp = 0, tot_w_nz = 0, tot_wout = 0, tot_xaug = 0, tot_fb = 0;
+    int64_t tot_wlm = 0;  // elements of the transposed local-model blocks (pool d_wlm)
+    int64_t tot_a_ell = 0, tot_w_ell = 0, tot_a_om = 0, tot_a_oe = 0;
+    int maxn = 0, maxninp = 0;
+};
+
+PoolPlan plan_pools(const PoolPlanIn &in);
+
+// ------------------------------------------------------------------ one region's weights
+// what sml_res_load_region uploads, in the storage dtype: A and W_in as CSR, W_out
+// transposed and padded (wt [nout_pad][ld]) with its local-model block (wl [ncs][nout_pad]),
+// and the ELL copies where the region's rows fit them (RegionDev; empty otherwise)
+template <typename StoT>
+struct PackedRegion {
+    std::vector<int32_t> rp, wrp;
+    std::vector<uint16_t> acol, wcol;
+    std::vector<StoT> aval, wval, wt, wl;
+    std::vector<uint16_t> a_ec, w_ec;  // ELL columns: A pair-major, W_in [n]
+    std::vector<StoT> a_ev, w_ev;
+    std::vector<uint64_t> om;  // A's overflow bits, one word per 64 rows
+    std::vector<uint32_t> ob;  // overflow entries before each word
+    std::vector<uint16_t> oc;  // overflow entries: column
+    std::vector<StoT> ovv;     //                   value
+    int a_w = 0, a_ov = 0, w_w = 0, w_q = 0;
+    uint32_t w_magic = 0;
+    int64_t wnz = 0;
+};
+
+struct PackIn {
+    int i;  // the region's local index (error messages)
+    int k, ncs, nout, nout_pad;
+    int a_ell_cap, w_ell_cap;
+};
+
+// rows / cols / vals: A as COO, 1-based, k entries; win(n, ninp) and wout(nout, ncs + n)
+// column-major.  fp32 storage demands exact representability.
+template <typename SrcT, typename StoT>
+int pack_region(const PackIn &in, const RegionDev &rg, const int *rows, const int *cols, const SrcT *vals,
+                const SrcT *win, const SrcT *wout, PackedRegion<StoT> *out);
+
+// ------------------------------------------------------------------ index tables
+struct TablesIn {
+    int numregions, nlocal, ncs, nout;
+    const RegionGeom *geom;    // [nlocal]
+    const unsigned char *sst;  // [nlocal]
+    const int *ninp;           // [nlocal]
+    const RegionDev *rd;       // [nlocal] (fb)
+    int64_t tot_fb;
+    const int8_t *out_l;  // generic context: [nout] unstandardise slots (no other table); else null
+};
+
+struct RegionTables {
+    std::vector<int32_t> asm_dst;  // [numregions*nout] -> concatenated grid index
+    std::vector<int32_t> fb_src;   // [tot_fb]
+    std::vector<uint8_t> fb_l;
+    std::vector<uint16_t> fb_reg;
+    std::vector<int32_t> lm_src;  // [nlocal*ncs]
+    std::vector<uint8_t> lm_l;
+    std::vector<int32_t> tisr_fb, tisr_grid;  // feedback index, grid2d index of the overlap-tile point
+    std::vector<uint16_t> tisr_reg;           // local region
+    std::vector<int8_t> outl;                 // [nout] mean / std slot of each output
+    std::vector<int32_t> tgt_idx;             // [nlocal][nout] the targets' positions in each region's feedback
+};
+
+int build_region_tables(const TablesIn &in, RegionTables *out);
+
+// mean/std index (0-based) of output o of the bottom-level 2x2 reservoir:
+// atmo (var,x,y,z) -> (var-1)*8+z, logp -> 33, precip -> 35 (1-based; :1815-1846)
+int out_std_index(int o, const RegionGeom &g);
+
+// the balanced update: the region each of G blocks' share of the rows starts in
+// (row0 [nlocal+1] = the regions' rows concatenated)
+std::vector<int32_t> block_first_regions(const std::vector<int32_t> &row0, int G);
+
+// sml_res_footprint: unpadded weight bytes, and the minimal traffic of a step
+// (wb: bytes per stored weight)
+void footprint(int nlocal, const int *n, const int *k, const int *ninp, int ncs, int nout, int64_t wb,
+               int64_t *weight_bytes, int64_t *algo_bytes);
+
+}  // namespace sml
