@@ -142,7 +142,7 @@ static __device__ long long g_pst[kIL * 32];
 
 // phypar's pieces (phy_phypar.f90:79-196), composed by phys_column in the
 // reference's order; k_st_gridspec also runs the moist / diffusion part and the
-// longwave / surface part of a column on different waves (sml_dynamics.hip).
+// longwave / surface part of a column on different waves (sml_dyn_fused.hpp).
 // 1.2 thermodynamic variables (phy_phypar.f90:79-94)
 struct PhysThermo {
     double psg, rps;

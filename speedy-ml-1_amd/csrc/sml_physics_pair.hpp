@@ -1,6 +1,6 @@
 // sml_physics_pair.hpp -- phypar's longwave / surface side (and, on a shortwave step, its
 // shortwave) on two lanes per column: the row kernel whose three roles each have waves
-// of their own (k_st_gridspec_p, sml_dynamics.hip).
+// of their own (k_st_gridspec_p, sml_dyn_fused.hpp).
 //
 // Reference: phypar (src/phy_phypar.f90:121-179) -- radsw (phy_radiat.f90:154-328), radlw
 // (:330-458), suflux (phy_suflux.f90:1-355) -- with the expressions of sml_physics.hpp.

@@ -16,7 +16,7 @@ a*b + c come from the compiler, so a toolchain change may move bits in both the 
 and the new kernel: the file stores the `hipcc --version` string it was made with, and
 after a toolchain change it has to be regenerated from a build WITHOUT the successor
 edits of that split (check the split's commit out, revert the split in
-sml_physics_pair.hpp / sml_dynamics.hip, build, run this script), never from the
+sml_physics_pair.hpp / sml_dyn_fused.hpp, build, run this script), never from the
 kernel under test.
 
 A case (run_case): the seeded synthetic state dyn_state(SEED) with its spectral

@@ -350,3 +350,55 @@ def test_run_model_without_gpu_physics_is_window_plus_q_floor(cuda):
     finally:
         d.close()
         ref.close()
+
+
+@pytest.mark.parametrize("nograph", [False, True])
+@pytest.mark.parametrize("physics", [True, False])
+def test_window_keeps_its_three_impint_slots(cuda, monkeypatch, physics, nograph):
+    """A window holds three impint tables at once (delt / 2, delt, 2 delt) in a cache of
+    four slots.  Five earlier impint calls leave the slots [k5, delt / 2, k3, k4] with the
+    next eviction due at the slot of delt / 2: the window finds delt / 2 there, and its
+    miss on delt must not take that slot from under step(1, 1).  Bitwise the window of a
+    fresh context."""
+    from speedy_ml_amd.dynamics import DELT
+
+    mp = monkeypatch if nograph else None
+    a, b = _ctx(physics=physics, nograph=mp), _ctx(physics=physics, nograph=mp)
+    try:
+        for dt in (0.3 * DELT, 0.5 * DELT, 0.7 * DELT, 0.9 * DELT, 1.1 * DELT):
+            a.impint(dt)
+        a.window(1)
+        b.window(1)
+        sa, sb = a.get_state(), b.get_state()
+        for f in sa:
+            np.testing.assert_array_equal(sa[f], sb[f], err_msg=f)
+        assert a.get_clock() == b.get_clock()
+    finally:
+        a.close()
+        b.close()
+
+
+def test_context_create_destroy_repeats(cuda):
+    """Eight contexts in one process, each created, run for one run_model window, asked
+    for run_speedy and closed while its check stream, events, graphs and lazily allocated
+    words are live: every forecast is bitwise the first and every window is safe."""
+    import torch
+
+    g4, g2 = _grids()
+    i4, i2 = _t(g4, cuda), _t(g2, cuda)
+    first = None
+    for rnd in range(8):
+        d = _ctx()
+        try:
+            o4, o2 = torch.zeros_like(i4), torch.zeros_like(i2)
+            d.run_model(i4, i2, o4, o2, nleap=1)
+            safe, mm = d.last_safe()
+        finally:
+            d.close()
+        assert safe, (rnd, mm)
+        torch.cuda.synchronize()
+        out = (o4.cpu().numpy(), o2.cpu().numpy())
+        if first is None:
+            first = out
+        for x, y in zip(out, first):
+            np.testing.assert_array_equal(x, y, err_msg="round %d" % rnd)
