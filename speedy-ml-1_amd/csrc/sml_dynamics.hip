@@ -57,60 +57,12 @@ SML_TL_DEFINE(dynamics)
 #include "sml_dyn_io.hpp"
 #include "sml_dyn_forcing.hpp"
 // clang-format on
+#include "sml_devmem.hpp"
 #include "sml_dyn_cache.hpp"
 
 using namespace sml;
 
 namespace {
-
-// Every device and pinned allocation of a context.  A buffer is named once, where it is
-// allocated, with its size; all of them are freed together when the context goes.
-// Memory comes zero-filled, and the fill is complete when the request returns (a buffer
-// asked for in mid-run is then safe on any stream); zero = false leaves that out for a
-// buffer whose every word is written before it is read.  The first failure sticks: later requests do nothing and
-// status() reports it, so a list of allocations needs one check at its end.
-class DevMem {
-public:
-    DevMem() = default;
-    DevMem(const DevMem &) = delete;
-    DevMem &operator=(const DevMem &) = delete;
-    ~DevMem() {
-        for (void *p : dev_) (void)hipFree(p);
-        for (void *p : pinned_) (void)hipHostFree(p);
-    }
-    template <typename T>
-    int device(T **p, size_t count, bool zero = true) {
-        *p = nullptr;
-        if (rc_) return rc_;
-        void *v = nullptr;
-        if (hipError_t e = hipMalloc(&v, count * sizeof(T)); e != hipSuccess) return fail_hip(e);
-        dev_.push_back(v);
-        if (zero) {
-            if (hipError_t e = hipMemset(v, 0, count * sizeof(T)); e != hipSuccess) return fail_hip(e);
-            if (hipError_t e = hipDeviceSynchronize(); e != hipSuccess) return fail_hip(e);
-        }
-        *p = static_cast<T *>(v);
-        return SML_OK;
-    }
-    template <typename T>
-    int pinned(T **p, size_t count, unsigned flags) {
-        *p = nullptr;
-        if (rc_) return rc_;
-        void *v = nullptr;
-        if (hipHostMalloc(&v, count * sizeof(T), flags) != hipSuccess)
-            return rc_ = fail(SML_ERR_NOMEM, "pinned allocation of %zu bytes failed", count * sizeof(T));
-        pinned_.push_back(v);
-        std::memset(v, 0, count * sizeof(T));
-        *p = static_cast<T *>(v);
-        return SML_OK;
-    }
-    int status() const { return rc_; }
-
-private:
-    int fail_hip(hipError_t e) { return rc_ = fail(SML_ERR_HIP, "device allocation: %s", hipGetErrorString(e)); }
-    std::vector<void *> dev_, pinned_;
-    int rc_ = SML_OK;
-};
 
 struct GraphRelease {
     void operator()(hipGraphExec_t &g) const {

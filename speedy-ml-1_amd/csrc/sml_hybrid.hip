@@ -33,6 +33,7 @@
 #include <cstdlib>
 #include <vector>
 
+#include "sml_devmem.hpp"
 #include "sml_internal.hpp"
 #include "sml_timeline.hpp"
 
@@ -46,6 +47,7 @@ struct sml_comm {
 };
 
 struct sml_hybrid {
+    DevMem mem;  // first: every device and pinned buffer below is its; freed last, after the streams
     sml_reservoirs *res = nullptr;
     sml_dynamics *dyn = nullptr;
     sml_comm *comm = nullptr;
@@ -479,20 +481,15 @@ int hop_wait(sml_hybrid *h, int k, hipStream_t s) {
 // all-gather's send / receive slabs (when the communicator has a transport) and the
 // region-order copy of uneven shares
 int alloc_exchange(sml_hybrid *h) {
-    for (double **p : {&h->d_send, &h->d_recv, &h->d_glob})
-        if (*p) {
-            (void)hipFree(*p);
-            *p = nullptr;
-        }
-    const size_t row = (size_t)h->xw * 8;
+    for (double **p : {&h->d_send, &h->d_recv, &h->d_glob}) h->mem.release(p);
+    const size_t row = (size_t)h->xw;
     const int world = h->comm->world;
-    if (h->comm->comm && h->maxc > 0 &&
-        (hipMalloc(&h->d_send, (size_t)h->maxc * row) != hipSuccess ||
-         hipMalloc(&h->d_recv, (size_t)world * h->maxc * row) != hipSuccess ||
-         hipMemset(h->d_send, 0, (size_t)h->maxc * row) != hipSuccess))
-        return fail(SML_ERR_NOMEM, "exchange buffers");
-    if (!h->contiguous && hipMalloc(&h->d_glob, (size_t)h->numregions * row) != hipSuccess)
-        return fail(SML_ERR_NOMEM, "exchange buffers");
+    if (h->comm->comm && h->maxc > 0) {
+        h->mem.device(&h->d_send, (size_t)h->maxc * row);  // (zero: its padding rows are sent as they are)
+        h->mem.device(&h->d_recv, (size_t)world * h->maxc * row, false);
+    }
+    if (!h->contiguous) h->mem.device(&h->d_glob, (size_t)h->numregions * row, false);
+    if (h->mem.status()) return fail(SML_ERR_NOMEM, "exchange buffers");
     return SML_OK;
 }
 
@@ -623,12 +620,6 @@ extern "C" int sml_hybrid_destroy(sml_hybrid *h) {
     }
     for (hipEvent_t e : h->ev)
         if (e) (void)hipEventDestroy(e);
-    sml_hybrid::Slab &sl = h->slab;
-    void *ptrs[] = {h->d_send, h->d_recv, h->d_glob, h->d_perm, h->d_seq, sl.d_fb, sl.d_ov, sl.d_ring, sl.d_sst, sl.d_ms,
-                    sl.d_ring_src, sl.d_row, sl.d_sst_src, sl.d_sfb, sl.d_sgrid, sl.d_sreg};
-    for (void *p : ptrs)
-        if (p) (void)hipFree(p);
-    if (h->h_late) (void)hipHostFree(h->h_late);
     delete h;
     return SML_OK;
 }
@@ -713,12 +704,9 @@ extern "C" int sml_hybrid_create(sml_reservoirs *res, sml_dynamics *dyn, sml_com
     for (hipEvent_t &e : h->ev)
         if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) return bail(fail(SML_ERR_HIP, "event"));
     if (int rc = sml_hybrid_set_hop_mode(h, SML_HOP_AUTO)) return bail(rc);
-    constexpr size_t seq_bytes = sml_hybrid::kHops * sml_hybrid::kSeqStride * sizeof(uint64_t);
-    if (hipMalloc(&h->d_seq, seq_bytes) != hipSuccess || hipMemset(h->d_seq, 0, seq_bytes) != hipSuccess ||
-        hipHostMalloc((void **)&h->h_late, sizeof(unsigned), hipHostMallocCoherent) != hipSuccess ||
-        hipDeviceSynchronize() != hipSuccess)
-        return bail(fail(SML_ERR_HIP, "sequence counters"));
-    *h->h_late = 0;
+    h->mem.device(&h->d_seq, (size_t)sml_hybrid::kHops * sml_hybrid::kSeqStride);
+    h->mem.pinned(&h->h_late, 1, hipHostMallocCoherent);
+    if (h->mem.status()) return bail(fail(SML_ERR_HIP, "sequence counters"));
     h->xw = h->nout;
     if (world > 1) {
         std::vector<int32_t> perm(h->numregions);
@@ -726,7 +714,7 @@ extern "C" int sml_hybrid_create(sml_reservoirs *res, sml_dynamics *dyn, sml_com
         if (int rc = sml_exchange_plan(h->numregions, world, &h->maxc, &contig, perm.data())) return bail(rc);
         h->contiguous = contig != 0;
         if (!h->contiguous &&
-            (hipMalloc(&h->d_perm, (size_t)h->numregions * 4) != hipSuccess ||
+            (h->mem.device(&h->d_perm, (size_t)h->numregions, false) != SML_OK ||
              hipMemcpy(h->d_perm, perm.data(), perm.size() * 4, hipMemcpyHostToDevice) != hipSuccess))
             return bail(fail(SML_ERR_NOMEM, "exchange buffers"));
         if (int rc = alloc_exchange(h)) return bail(rc);
@@ -909,8 +897,8 @@ int slab_sst(sml_hybrid *h, const double *d_all, hipStream_t m) {
 }
 
 template <typename T>
-int upload(T **d, const std::vector<T> &v) {
-    if (hipMalloc(d, std::max<size_t>(v.size(), 1) * sizeof(T)) != hipSuccess) return fail(SML_ERR_NOMEM, "slab tables");
+int upload(sml_hybrid *h, T **d, const std::vector<T> &v) {
+    if (h->mem.device(d, std::max<size_t>(v.size(), 1), false)) return fail(SML_ERR_NOMEM, "slab tables");
     if (!v.empty()) SML_HIP(hipMemcpy(*d, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
     return SML_OK;
 }
@@ -993,19 +981,18 @@ extern "C" int sml_hybrid_set_slab(sml_hybrid *h, sml_reservoirs *slab, const do
     sl.mask = d_sea_mask;
     sl.tot_fb = (int)ring_src.size();
     sl.n_sst_el = (int)sfb.size();
-    if (int rc = upload(&sl.d_ring_src, ring_src)) return rc;
-    if (int rc = upload(&sl.d_row, row)) return rc;
-    if (int rc = upload(&sl.d_sst_src, src)) return rc;
-    if (int rc = upload(&sl.d_sfb, sfb)) return rc;
-    if (int rc = upload(&sl.d_sgrid, sgrid)) return rc;
-    if (int rc = upload(&sl.d_sreg, sreg)) return rc;
-    if (hipMalloc(&sl.d_fb, std::max<size_t>(sl.tot_fb, 1) * 8) != hipSuccess ||
-        hipMalloc(&sl.d_ov, std::max<size_t>((size_t)nslab * snout, 1) * 8) != hipSuccess ||
-        hipMalloc(&sl.d_ring, std::max<size_t>((size_t)(sl.ratio - 1) * sl.tot_fb, 1) * 8) != hipSuccess ||
-        hipMalloc(&sl.d_sst, (size_t)kGrid2d * 8) != hipSuccess ||
-        hipMalloc(&sl.d_ms, std::max<size_t>((size_t)2 * nslab, 1) * 8) != hipSuccess)
-        return fail(SML_ERR_NOMEM, "slab buffers");
-    SML_HIP(hipMemset(sl.d_sst, 0, (size_t)kGrid2d * 8));
+    if (int rc = upload(h, &sl.d_ring_src, ring_src)) return rc;
+    if (int rc = upload(h, &sl.d_row, row)) return rc;
+    if (int rc = upload(h, &sl.d_sst_src, src)) return rc;
+    if (int rc = upload(h, &sl.d_sfb, sfb)) return rc;
+    if (int rc = upload(h, &sl.d_sgrid, sgrid)) return rc;
+    if (int rc = upload(h, &sl.d_sreg, sreg)) return rc;
+    h->mem.device(&sl.d_fb, std::max<size_t>(sl.tot_fb, 1), false);
+    h->mem.device(&sl.d_ov, std::max<size_t>((size_t)nslab * snout, 1), false);
+    h->mem.device(&sl.d_ring, std::max<size_t>((size_t)(sl.ratio - 1) * sl.tot_fb, 1), false);
+    h->mem.device(&sl.d_sst, (size_t)kGrid2d);
+    h->mem.device(&sl.d_ms, std::max<size_t>((size_t)2 * nslab, 1), false);
+    if (h->mem.status()) return fail(SML_ERR_NOMEM, "slab buffers");
     h->xw = xw;
     if (int rc = sml_res_set_outvec_ld(h->res, xw)) return rc;
     if (h->res_cus > 0)  // the slab step runs on the main stream too

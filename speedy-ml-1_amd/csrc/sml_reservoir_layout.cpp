@@ -60,6 +60,40 @@ PoolPlan plan_pools(const PoolPlanIn &in) {
     return p;
 }
 
+StepShape step_shape(const StepShapeIn &in) {
+    StepShape s;
+    s.lds_x = (in.maxn + 1) / 2 * 2;
+    s.lds_buf = s.lds_x + in.maxninp;
+    s.lds_region = (size_t)s.lds_buf * sizeof(double);
+    s.lds_bal = 2 * s.lds_region;
+    s.lds_drive = 2 * s.lds_region;
+    s.region_lds = s.lds_region <= kRegionLdsMax;
+    // parts per region: enough blocks to fill the 512 resident 1024-thread block slots
+    // (2 per CU with ~54 KB LDS each) once, each part at least one 1024-row pass.  Every
+    // part stages the region's whole x, so more parts cost HBM traffic: measured on
+    // 1152 regions, 1 part 119 us, 2 parts 128 us, 4 parts 165 us (profiles/r01m)
+    const int max_parts = std::max(1, (in.maxn + kUpdThreads - 1) / kUpdThreads);
+    s.parts = in.nlocal > 0 ? std::max(1, std::min(max_parts, (512 + in.nlocal - 1) / in.nlocal)) : 1;
+    s.wide = in.nout_pad % kRowsWide == 0 && in.nout_pad / kRowsWide <= kWideMax;
+    s.rows = s.wide ? kRowsWide : kRows;
+    s.groups = in.nout_pad / s.rows;
+    s.wpb = s.wide ? kWideWaves : 4;
+    // the balanced update needs every region in ELL form, a segment's x and u within one
+    // staging round (kStageX entries of x, one of u, per thread) and two buffers in LDS
+    s.balanced = !in.per_region && in.nlocal > 0 && in.ell_ok && in.maxn <= kStageX * kUpdThreads &&
+                 in.maxninp <= kUpdThreads && s.lds_bal <= in.max_lds;
+    // the fused begin needs the wide readout (a wave per item of a region in one block)
+    // and the update's LDS staging (2 blocks per CU)
+    s.begin_fused = in.begin_mode > 0 && s.wide && s.region_lds;
+    // the grouped finish: outputs in quads, kFinGroups column groups of kFinGsz at most,
+    // a thread per (quad, group) in a block of 256
+    s.finish_grouped = in.ncs > 0 && in.nout_pad % 4 == 0 && in.nout_pad <= kFinOutMax &&
+                       in.nout_pad / 4 * kFinGroups <= 256 && (in.ncs + kFinGroups - 1) / kFinGroups <= kFinGsz &&
+                       !in.finish_ungrouped;
+    s.drive_fused = !in.stepwise_drive && s.lds_drive <= in.max_lds;
+    return s;
+}
+
 template <typename SrcT, typename StoT>
 int pack_region(const PackIn &in, const RegionDev &rg, const int *rows, const int *cols, const SrcT *vals,
                 const SrcT *win, const SrcT *wout, PackedRegion<StoT> *out) {

@@ -71,6 +71,52 @@ struct PoolPlan {
 
 PoolPlan plan_pools(const PoolPlanIn &in);
 
+// ------------------------------------------------------------------ the launch shape
+// constants the kernels (sml_res_*.hpp) and the shape below share
+constexpr int kUpdThreads = 1024;  // threads per update block (one row per thread per pass)
+constexpr int kStageX = 7;         // the balanced update stages kStageX * kUpdThreads state entries per segment
+constexpr int kRowsWide = 17;   // rows per wave when nout_pad = 17 w (w <= 8 waves)
+constexpr int kWideWaves = 2;   // waves per readout block with kRowsWide rows (a region = w / 2 blocks;
+                                // 2 / 4 / 8 waves measured: one-pass 0.638 / 0.644 / 0.696 ms)
+constexpr int kBeginThreads = 512;  // threads per fused-begin block: a wave per wide readout item
+constexpr int kWideMax = 8;         // the wide readout's bound on w, one region's items in one begin block
+static_assert(kWideMax == kBeginThreads / 64, "the fused begin runs a wave per wide readout item");
+constexpr int kMaxNcs = 256;     // local-model length bound of the fused finish (132 in T30L8)
+constexpr int kFinGroups = 7;
+constexpr int kFinGsz = 19;  // the grouped finish's column-group bound (ncs 132: 6 x 19 + 18)
+constexpr int kFinOutMax = 144;  // the grouped finish's outputs (its LDS rows), taken in quads by 256 threads
+constexpr size_t kRegionLdsMax = 64 * 1024;  // a per-region block's LDS staging: two blocks per CU
+
+struct StepShapeIn {
+    int maxn, maxninp, nout_pad, ncs, nlocal;
+    size_t max_lds;  // the device's LDS per workgroup
+    bool ell_ok;     // every local region's A and W_in in ELL form
+    int begin_mode;  // sml_res_set_begin_mode
+    bool per_region, finish_ungrouped, stepwise_drive;  // sml_res_set_reference_paths
+};
+
+// Which kernel form each stage of a step takes and with what LDS: all of it host
+// arithmetic on the context's sizes and switches, worked out when one of them changes
+// (create, a region's load, the setters) and read by the launchers and by the ABI's
+// reports (sml_res_update_balanced, sml_res_begin_fused).
+struct StepShape {
+    int lds_x = 0;          // the update's LDS row count: maxn rounded up to even
+    int lds_buf = 0;        // doubles of one staging buffer: lds_x of x, then maxninp of u
+    size_t lds_region = 0;  // k_res_update / k_res_begin: x and u of the largest region
+    size_t lds_bal = 0;     // k_res_update_bal: two such buffers
+    size_t lds_drive = 0;   // k_res_drive: two states and two inputs
+    bool region_lds = false;  // the per-region update stages in LDS (else gathers from global memory)
+    int parts = 1;            // blocks per region of the per-region update
+    bool wide = false;        // the readout kRowsWide rows a wave (nout_pad = 17 w, w <= kWideMax)
+    int rows = kRows, groups = 0, wpb = 4;  // rows per wave, items per region, waves per block
+    bool balanced = false;        // k_res_update_bal (else k_res_update)
+    bool begin_fused = false;     // k_res_begin (else the update grid, then the v_ml readout grid)
+    bool finish_grouped = false;  // k_res_finish_grid in column groups (else one thread per output)
+    bool drive_fused = false;     // k_res_drive (else a column writer and an update per column)
+};
+
+StepShape step_shape(const StepShapeIn &in);
+
 // ------------------------------------------------------------------ one region's weights
 // what sml_res_load_region uploads, in the storage dtype: A and W_in as CSR, W_out
 // transposed and padded (wt [nout_pad][ld]) with its local-model block (wl [ncs][nout_pad]),

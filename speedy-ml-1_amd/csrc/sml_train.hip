@@ -29,9 +29,11 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <new>
 #include <vector>
 
+#include "sml_devmem.hpp"
 #include "sml_internal.hpp"
 
 using namespace sml;
@@ -967,6 +969,7 @@ __global__ __launch_bounds__(256, 2) void k_solve_lpanel(const double *__restric
 }  // namespace
 
 struct sml_train {
+    DevMem mem;  // first: every device buffer below is its; all freed together with the context
     int nlocal = 0, nout = 0, npad = 0, C = 0;
     int panel = kPanel;  // block columns per Cholesky panel (sml_train_set_panel)
     std::vector<int> naug;
@@ -983,9 +986,6 @@ struct sml_train {
 
 extern "C" int sml_train_destroy(sml_train *t) {
     if (!t) return SML_OK;
-    void *ptrs[] = {t->d_regs, t->d_G, t->d_B, t->d_wout_off, t->d_info, t->d_linv};
-    for (void *p : ptrs)
-        if (p) (void)hipFree(p);
     if (t->ev_fork) (void)hipEventDestroy(t->ev_fork);
     if (t->ev_join) (void)hipEventDestroy(t->ev_join);
     if (t->fwd) (void)hipStreamDestroy(t->fwd);
@@ -998,32 +998,31 @@ extern "C" int sml_train_create(int nlocal, const int *naug, int nout, sml_train
     // k_train_gram2 loads rows in pairs, clamped to (rows - 2, rows - 1): an operand of one row has no pair
     SML_REQUIRE(nout >= 2 && nout <= kRhs, "nout must be in 2..144");
     *out = nullptr;
-    sml_train *t = new (std::nothrow) sml_train();
+    // (the context is the owner's until the last step has passed: every refusal below frees all of it)
+    std::unique_ptr<sml_train, int (*)(sml_train *)> owner(new (std::nothrow) sml_train(), sml_train_destroy);
+    sml_train *t = owner.get();
     if (!t) return fail(SML_ERR_NOMEM, "host allocation failed");
     t->nlocal = nlocal;
     t->nout = nout;
     t->naug.assign(naug, naug + nlocal);
     int mx = 0;
     for (int i = 0; i < nlocal; ++i) {
-        if (naug[i] < 2) {
-            delete t;
-            return fail(SML_ERR_ARG, "naug[%d] = %d (must be >= 2)", i, naug[i]);
-        }
+        SML_REQUIRE(naug[i] >= 2, "naug[%d] = %d (must be >= 2)", i, naug[i]);
         mx = naug[i] > mx ? naug[i] : mx;
     }
     t->npad = (mx + kTile - 1) / kTile * kTile;  // uniform padded size: one batched solve
     t->C = t->npad / kTile;
     const size_t g = (size_t)nlocal * t->npad * t->npad, b = (size_t)nlocal * t->npad * nout;
-    hipError_t e;
-    if ((e = hipMalloc(&t->d_G, g * 8)) != hipSuccess || (e = hipMalloc(&t->d_B, b * 8)) != hipSuccess ||
-        (e = hipMalloc(&t->d_regs, nlocal * sizeof(TrainRegion))) != hipSuccess ||
-        (e = hipMalloc(&t->d_wout_off, nlocal * sizeof(long long))) != hipSuccess ||
-        (e = hipMalloc(&t->d_info, nlocal * sizeof(int))) != hipSuccess ||
-        (e = hipMalloc(&t->d_linv, (size_t)nlocal * t->C * kTile * kTile * 8)) != hipSuccess) {
-        sml_train_destroy(t);
-        return fail(SML_ERR_NOMEM, "sml_train_create: %s (%.2f GB of Gram matrices)", hipGetErrorString(e),
-                    g * 8e-9);
-    }
+    // (none filled here: sml_train_reset clears G and B, the tables are uploaded below,
+    // info and the inverses are written by the solve before it reads them)
+    t->mem.device(&t->d_G, g, false);
+    t->mem.device(&t->d_B, b, false);
+    t->mem.device(&t->d_regs, nlocal, false);
+    t->mem.device(&t->d_wout_off, nlocal, false);
+    t->mem.device(&t->d_info, nlocal, false);
+    t->mem.device(&t->d_linv, (size_t)nlocal * t->C * kTile * kTile, false);
+    if (t->mem.status())
+        return fail(SML_ERR_NOMEM, "sml_train_create: device allocation failed (%.2f GB of Gram matrices)", g * 8e-9);
     std::vector<long long> wo(nlocal);
     std::vector<TrainRegion> regs(nlocal);
     long long off = 0, pre = 0;
@@ -1043,8 +1042,9 @@ extern "C" int sml_train_create(int nlocal, const int *naug, int nout, sml_train
                                     (int)kDiagBLds));
         lds_set = true;
     }
-    *out = t;
-    return sml_train_reset(t, nullptr);
+    if (int rc = sml_train_reset(t, nullptr)) return rc;
+    *out = owner.release();
+    return SML_OK;
 }
 
 extern "C" int sml_train_reset(sml_train *t, void *stream) {
@@ -1234,8 +1234,10 @@ extern "C" int sml_probe_mfma_f64_clock(int iters, double *tflops, double *ghz) 
     const int blocks = ncu * 2;  // 8 waves per CU = 2 per SIMD
     double *sink = nullptr;
     long long *stamps = nullptr;
-    SML_HIP(hipMalloc(&sink, 8));
-    if (ghz) SML_HIP(hipMalloc(&stamps, (size_t)2 * blocks * sizeof(long long)));
+    DevMem mem;  // (the two probe buffers, freed at every return)
+    mem.device(&sink, 1);
+    if (ghz) mem.device(&stamps, (size_t)2 * blocks);
+    if (int rc = mem.status()) return rc;
     hipEvent_t e0, e1;
     SML_HIP(hipEventCreate(&e0));
     SML_HIP(hipEventCreate(&e1));
@@ -1248,13 +1250,11 @@ extern "C" int sml_probe_mfma_f64_clock(int iters, double *tflops, double *ghz) 
     SML_HIP(hipEventElapsedTime(&ms, e0, e1));
     (void)hipEventDestroy(e0);
     (void)hipEventDestroy(e1);
-    (void)hipFree(sink);
     const double flops = (double)blocks * 4 * iters * 8 * 2.0 * 16 * 16 * 4;
     *tflops = flops / (ms * 1e-3) / 1e12;
     if (ghz) {
         std::vector<long long> h((size_t)2 * blocks);
         SML_HIP(hipMemcpy(h.data(), stamps, h.size() * sizeof(long long), hipMemcpyDeviceToHost));
-        (void)hipFree(stamps);
         std::vector<double> f;
         for (int b = 0; b < blocks; ++b)
             if (h[2 * b + 1] > 0) f.push_back((double)h[2 * b] / (double)h[2 * b + 1] * 0.1);  // 100 MHz -> GHz

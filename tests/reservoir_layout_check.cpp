@@ -409,6 +409,201 @@ static void check_tables() {
               gt.tisr_fb.empty() && gt.tisr_grid.empty() && gt.tisr_reg.empty() && gt.tgt_idx.empty(), "a generic context has only outl");
 }
 
+// ---------------------------------------------------------------- the step's shape
+// step_shape against the predicates as the launchers used to spell them, each where it
+// was used, with their numbers written out (1024 threads, 7 staged entries, 17 rows and
+// 8 waves, 7 groups of 19, 64 KiB): on both sides of every edge, then a random sweep.
+struct WantShape {
+    int lds_x, lds_buf, parts, rows, groups, wpb;
+    size_t lds_region, lds_bal, lds_drive;
+    bool region_lds, wide, balanced, begin_fused, finish_grouped, drive_fused;
+};
+
+static WantShape want_shape(const StepShapeIn &in) {
+    WantShape w;
+    // launch_update
+    const int max_parts = std::max(1, (in.maxn + 1024 - 1) / 1024);
+    w.parts = in.nlocal ? std::max(1, std::min(max_parts, (512 + in.nlocal - 1) / in.nlocal)) : 1;
+    w.lds_x = (in.maxn + 1) / 2 * 2;
+    w.lds_buf = w.lds_x + in.maxninp;
+    w.lds_region = (size_t)(w.lds_x + in.maxninp) * sizeof(double);
+    w.region_lds = w.lds_region <= 64 * 1024;
+    // bal_usable / launch_update_bal
+    w.lds_bal = 2 * (size_t)((in.maxn + 1) / 2 * 2 + in.maxninp) * sizeof(double);
+    w.balanced = !in.per_region && in.nlocal != 0 && in.ell_ok && in.maxn <= 7 * 1024 && in.maxninp <= 1024 &&
+                 w.lds_bal <= in.max_lds;
+    // begin_fusable (kBeginThreads / 64 = 512 / 64)
+    w.begin_fused = in.begin_mode > 0 && in.nout_pad % 17 == 0 && in.nout_pad / 17 <= 512 / 64 &&
+                    (size_t)(w.lds_x + in.maxninp) * sizeof(double) <= 64 * 1024;
+    // launch_readout
+    w.wide = in.nout_pad % 17 == 0 && in.nout_pad / 17 <= 8;
+    w.rows = w.wide ? 17 : 8;
+    w.groups = in.nout_pad / w.rows;
+    w.wpb = w.wide ? 2 : 4;
+    // launch_finish_grid
+    w.finish_grouped = in.ncs > 0 && in.nout_pad % 4 == 0 && in.nout_pad <= 144 && in.nout_pad / 4 * 7 <= 256 &&
+                       (in.ncs + 7 - 1) / 7 <= 19 && !in.finish_ungrouped;
+    // drive_lds / sml_res_train_drive
+    w.lds_drive = 2 * (size_t)((in.maxn + 1) / 2 * 2 + in.maxninp) * sizeof(double);
+    w.drive_fused = !(in.stepwise_drive || w.lds_drive > in.max_lds);
+    return w;
+}
+
+static void check_shape_one(const StepShapeIn &in) {
+    const StepShape s = step_shape(in);
+    const WantShape w = want_shape(in);
+    CHECK(s.lds_x == w.lds_x && s.lds_buf == w.lds_buf, "lds_x %d %d lds_buf %d %d", s.lds_x, w.lds_x, s.lds_buf,
+          w.lds_buf);
+    CHECK(s.lds_region == w.lds_region && s.lds_bal == w.lds_bal && s.lds_drive == w.lds_drive,
+          "lds %zu %zu / %zu %zu / %zu %zu", s.lds_region, w.lds_region, s.lds_bal, w.lds_bal, s.lds_drive,
+          w.lds_drive);
+    CHECK(s.parts == w.parts, "parts %d %d", s.parts, w.parts);
+    CHECK(s.region_lds == w.region_lds, "region_lds %d %d", s.region_lds, w.region_lds);
+    CHECK(s.wide == w.wide && s.rows == w.rows && s.groups == w.groups && s.wpb == w.wpb,
+          "readout %d %d %d %d, want %d %d %d %d", s.wide, s.rows, s.groups, s.wpb, w.wide, w.rows, w.groups, w.wpb);
+    CHECK(s.balanced == w.balanced, "balanced %d %d", s.balanced, w.balanced);
+    CHECK(s.begin_fused == w.begin_fused, "begin_fused %d %d", s.begin_fused, w.begin_fused);
+    CHECK(s.finish_grouped == w.finish_grouped, "finish_grouped %d %d", s.finish_grouped, w.finish_grouped);
+    CHECK(s.drive_fused == w.drive_fused, "drive_fused %d %d", s.drive_fused, w.drive_fused);
+}
+
+static void check_shape() {
+    // the T30L8 hybrid context: n 6048, ninp 804 with sst, nout 136, ncs 132, 1152 regions
+    const StepShapeIn base{6048, 804, 136, 132, 1152, 163840, true, 0, false, false, false};
+    auto with = [&](const char *name, auto set) {
+        g_case = std::string("shape ") + name;
+        StepShapeIn in = base;
+        set(in);
+        check_shape_one(in);
+        return step_shape(in);
+    };
+    {   // the values the GPU tests pin (test_reservoir_edges_gpu.py), and the default's forms
+        const StepShape s = with("base", [](StepShapeIn &) {});
+        CHECK(s.balanced && !s.begin_fused && s.finish_grouped && s.drive_fused && s.wide && s.groups == 8 &&
+                  s.parts == 1 && s.lds_x == 6048,
+              "the default context's forms");
+    }
+    // maxn at kStageX * kUpdThreads, and the odd count below it (lds_x rounds up)
+    CHECK(with("maxn 7168", [](StepShapeIn &in) { in.maxn = 7168; }).balanced, "balanced at 7168");
+    CHECK(!with("maxn 7169", [](StepShapeIn &in) { in.maxn = 7169; }).balanced, "per region at 7169");
+    CHECK(with("maxn 7167", [](StepShapeIn &in) { in.maxn = 7167; }).lds_x == 7168, "odd maxn");
+    CHECK(with("maxninp 1024", [](StepShapeIn &in) { in.maxninp = 1024; }).balanced, "balanced at 1024");
+    CHECK(!with("maxninp 1025", [](StepShapeIn &in) { in.maxninp = 1025; }).balanced, "per region at 1025");
+    // the balanced and the drive LDS (2 (lds_x + maxninp) doubles) at max_lds and one row over
+    for (size_t max_lds : {(size_t)65536, (size_t)163840}) {
+        const int rows = (int)(max_lds / 16);  // lds_x + maxninp at the limit
+        for (int over : {0, 1}) {
+            const StepShape s = with("lds edge", [&](StepShapeIn &in) {
+                in.max_lds = max_lds;
+                in.maxninp = 500;
+                in.maxn = rows - 500 + 2 * over;  // (even: lds_x = maxn)
+            });
+            CHECK(s.lds_bal == max_lds + 32 * (size_t)over, "lds_bal %zu", s.lds_bal);
+            // (at 163840 the rows alone pass kStageX * kUpdThreads, so only the drive shows this edge)
+            CHECK(s.balanced == (!over && rows - 500 <= 7168), "balanced %d at max_lds %zu + %d", s.balanced,
+                  max_lds, over);
+            CHECK(s.drive_fused == !over, "drive_fused %d at max_lds %zu + %d", s.drive_fused, max_lds, over);
+        }
+        // the balanced edge below the row bound: more inputs than rows
+        for (int over : {0, 1}) {
+            const StepShape s = with("lds edge, wide u", [&](StepShapeIn &in) {
+                in.max_lds = max_lds;
+                in.maxninp = 1024;
+                in.maxn = std::min(rows - 1024, 7168) + 2 * over;
+            });
+            CHECK(s.balanced == !over, "balanced %d at max_lds %zu + %d", s.balanced, max_lds, over);
+        }
+    }
+    // the per-region LDS at 64 KiB and 8 bytes over
+    CHECK(with("region 64 KiB", [](StepShapeIn &in) { in.maxn = 8192 - 804; }).region_lds, "staged at 64 KiB");
+    CHECK(!with("region 64 KiB + 8", [](StepShapeIn &in) { in.maxn = 8192 - 804; in.maxninp = 805; }).region_lds,
+          "global at 64 KiB + 8");
+    for (int mode : {1, 2}) {
+        CHECK(with("fused 64 KiB", [&](StepShapeIn &in) { in.begin_mode = mode; in.maxn = 8192 - 804; }).begin_fused,
+              "fused at 64 KiB");
+        CHECK(!with("fused 64 KiB + 8", [&](StepShapeIn &in) {
+                   in.begin_mode = mode;
+                   in.maxn = 8192 - 804;
+                   in.maxninp = 805;
+               }).begin_fused,
+              "split at 64 KiB + 8");
+    }
+    // nout_pad: 17 * 8, 17 * 9 (a multiple of 17 past the waves; rounded to kRows it is 160, not wide
+    // either), a multiple of kRows that is none of 17
+    CHECK(with("nout_pad 136", [](StepShapeIn &in) { in.nout_pad = 136; in.begin_mode = 1; }).begin_fused, "136");
+    {
+        const StepShape s = with("nout_pad 153", [](StepShapeIn &in) { in.nout_pad = 153; in.begin_mode = 1; });
+        CHECK(!s.wide && !s.begin_fused && s.rows == 8, "153");
+    }
+    {
+        const StepShape s = with("nout_pad 144", [](StepShapeIn &in) { in.nout_pad = 144; in.begin_mode = 2; });
+        CHECK(!s.wide && !s.begin_fused && s.rows == 8 && s.groups == 18 && s.wpb == 4, "144");
+    }
+    CHECK(with("nout_pad 17", [](StepShapeIn &in) { in.nout_pad = 17; }).groups == 1, "17");
+    // the grouped finish
+    CHECK(with("ncs 133", [](StepShapeIn &in) { in.ncs = 133; }).finish_grouped, "ncs 133");
+    CHECK(!with("ncs 134", [](StepShapeIn &in) { in.ncs = 134; }).finish_grouped, "ncs 134");
+    CHECK(!with("ncs 0", [](StepShapeIn &in) { in.ncs = 0; }).finish_grouped, "ncs 0");
+    CHECK(with("finish 144", [](StepShapeIn &in) { in.nout_pad = 144; }).finish_grouped, "nout_pad 144");
+    CHECK(!with("finish 148", [](StepShapeIn &in) { in.nout_pad = 148; }).finish_grouped, "nout_pad 148");
+    CHECK(!with("finish 152", [](StepShapeIn &in) { in.nout_pad = 152; }).finish_grouped, "nout_pad 152");
+    CHECK(!with("ungrouped", [](StepShapeIn &in) { in.finish_ungrouped = true; }).finish_grouped, "the switch");
+    // parts: 512 block slots over the regions, a 1024-row pass each at least
+    CHECK(with("nlocal 1", [](StepShapeIn &in) { in.nlocal = 1; }).parts == 6, "nlocal 1");
+    CHECK(with("nlocal 1 small", [](StepShapeIn &in) { in.nlocal = 1; in.maxn = 1024; }).parts == 1, "one pass");
+    CHECK(with("nlocal 1 1025", [](StepShapeIn &in) { in.nlocal = 1; in.maxn = 1025; }).parts == 2, "two passes");
+    CHECK(with("nlocal 256", [](StepShapeIn &in) { in.nlocal = 256; }).parts == 2, "nlocal 256");
+    CHECK(with("nlocal 512", [](StepShapeIn &in) { in.nlocal = 512; }).parts == 1, "nlocal 512");
+    CHECK(with("nlocal 513", [](StepShapeIn &in) { in.nlocal = 513; }).parts == 1, "nlocal 513");
+    CHECK(with("nlocal 511", [](StepShapeIn &in) { in.nlocal = 511; }).parts == 2, "nlocal 511");
+    CHECK(!with("nlocal 0", [](StepShapeIn &in) { in.nlocal = 0; }).balanced, "nlocal 0");
+    // the begin modes, the reference-path switches alone, a region out of ELL form
+    CHECK(!with("mode 0", [](StepShapeIn &in) { in.begin_mode = 0; }).begin_fused, "mode 0");
+    CHECK(with("mode 1", [](StepShapeIn &in) { in.begin_mode = 1; }).begin_fused, "mode 1");
+    CHECK(with("mode 2", [](StepShapeIn &in) { in.begin_mode = 2; }).begin_fused, "mode 2");
+    {
+        const StepShape s = with("per region", [](StepShapeIn &in) { in.per_region = true; });
+        CHECK(!s.balanced && s.finish_grouped && s.drive_fused, "per_region alone");
+    }
+    {
+        const StepShape s = with("ungrouped alone", [](StepShapeIn &in) { in.finish_ungrouped = true; });
+        CHECK(s.balanced && !s.finish_grouped && s.drive_fused, "finish_ungrouped alone");
+    }
+    {
+        const StepShape s = with("stepwise", [](StepShapeIn &in) { in.stepwise_drive = true; });
+        CHECK(s.balanced && s.finish_grouped && !s.drive_fused, "stepwise_drive alone");
+    }
+    CHECK(!with("csr", [](StepShapeIn &in) { in.ell_ok = false; }).balanced, "a region in CSR form");
+    // a sweep around every edge at once
+    g_case = "shape sweep";
+    uint64_t rng = 0x9e3779b97f4a7c15ull;
+    auto next = [&](int n) {
+        rng = rng * 6364136223846793005ull + 1442695040888963407ull;
+        return (int)((rng >> 33) % (uint64_t)n);
+    };
+    const int maxns[] = {1, 2, 1023, 1024, 1025, 6048, 7167, 7168, 7169, 7388, 9216, 10240, 65535};
+    const int ninps[] = {1, 804, 805, 1023, 1024, 1025, 4096, 65535};
+    const int nouts[] = {8, 16, 17, 34, 136, 144, 148, 152, 153, 160, 272, 280};
+    const int ncss[] = {0, 1, 7, 19, 132, 133, 134, 256};
+    const int nlocals[] = {0, 1, 2, 255, 256, 511, 512, 513, 1152};
+    const size_t ldss[] = {0, 65536, 163840};
+    for (int t = 0; t < 6000; ++t) {
+        StepShapeIn in;
+        in.maxn = next(2) ? maxns[next(13)] : 1 + next(12000);
+        in.maxninp = next(2) ? ninps[next(8)] : 1 + next(2000);
+        in.nout_pad = next(2) ? nouts[next(12)] : 1 + next(300);
+        in.ncs = next(2) ? ncss[next(8)] : next(300);
+        in.nlocal = next(2) ? nlocals[next(9)] : next(1300);
+        in.max_lds = next(4) ? ldss[next(3)] : (size_t)16 * (in.maxn + in.maxninp + next(5) - 2);
+        in.ell_ok = next(4) != 0;
+        in.begin_mode = next(3);
+        in.per_region = next(4) == 0;
+        in.finish_ungrouped = next(4) == 0;
+        in.stepwise_drive = next(4) == 0;
+        check_shape_one(in);
+    }
+}
+
 int main() {
     std::vector<Case> cases;
     auto lens = [](int n, int base) { return std::vector<int>(n, base); };
@@ -493,6 +688,7 @@ int main() {
         for (bool csr : {false, true}) check_plan(ncs, ncs ? 136 : 8, csr);
     check_blocks();
     check_tables();
+    check_shape();
     std::printf("%d checks, %d failed\n", g_checks, g_fail);
     return g_fail != 0;
 }

@@ -3,7 +3,9 @@ test_reservoir_gpu.py: leakage != 1 through every update form, odd and tiny n, n
 the 1024-row pass, at the balanced update's 7168 bound, past the LDS-staged update
 (n + ninp > 8192) and at the 16-bit column limit, chunk_speedy not a multiple of 4,
 nout not a multiple of 8 (and padded wide rows, nout_pad 144), ninp > 1024 and > n,
-W_in with a stored column, the paced readout and a padded outvec stride.
+W_in with a stored column, the paced readout and a padded outvec stride; and the
+context itself: eight create / use / destroy rounds through every lazy allocation, the
+reported update and begin forms against the reference paths, refused creates.
 
 Reference: the oracle's predict (oracle.predict / predict_f32 with leakage= and
 chunk_speedy=), pinned at these shapes against a longdouble restatement by
@@ -595,3 +597,130 @@ def test_outvec_stride_generic_context(cuda):
     res.predict_finish(torch.from_numpy(lms[0, :, :ncs].copy()).to(cuda),
                        torch.zeros((2, nout), dtype=torch.float64, device=cuda))
     torch.cuda.synchronize()
+
+
+# ------------------------------------------- F. the context's memory, shape and refusals
+def _lifetime_round(cuda, ncu):
+    """One context through every allocation it makes after create: a W_in pool re-laid for
+    a second entry per row, the spectral radius's three buffers, the host step's staging
+    at two outvec strides, the balanced update's block tables at three grid sizes (8 and
+    16 share the first buffer, sized for the device; ncu + 8 grows it), timing events."""
+    import torch
+
+    ncs, nout, leak = 5, 9, 1 / 3
+    ws = [_weights(257, p, ncs, nout, seed=i) for i, p in enumerate((5, 33))]
+    fbs, lms = _series(ws, ncs, 5)
+    res = _generic(ws, ncs, nout, leak)
+    w = ws[0]
+    win2 = w.win.copy()
+    win2[(w.wcol + 1) % w.ninp, np.arange(w.n)] = 0.25
+    res.load_region(0, w.rows, w.cols, w.vals, win2, w.wout, w.mean, w.std)  # grow_win_pool
+    assert not res.ell_layout(0)["win_ell"] and not res.update_balanced()
+    got = {}
+    res.set_reference_paths(radius_global=True)
+    lo, hi, iters, info = res.spectral_radius()
+    assert (info == 0).all(), info
+    got["lo"], got["hi"], got["iters"] = lo, hi, iters
+    got["host"] = res.predict_host(fbs[0], lms[0, :, :ncs])
+    res.set_outvec_ld(nout + 3)  # the staging is re-sized for the stride
+    got["host_ld"] = res.predict_host(fbs[1], lms[1, :, :ncs])
+    res.load_region(0, w.rows, w.cols, w.vals, w.win, w.wout, w.mean, w.std)  # ELL form again
+    assert res.update_balanced()
+    res.enable_timing(2)
+    ov = torch.full((res.nlocal, nout + 3), float("nan"), dtype=torch.float64, device=cuda)
+    for t, cus in enumerate((8, 16, ncu + 8)):
+        res.set_update_cus(cus)
+        res.predict_begin(torch.from_numpy(fbs[2 + t].copy()).to(cuda))
+        res.predict_finish(torch.from_numpy(lms[2 + t, :, :ncs].copy()).to(cuda), ov)
+        torch.cuda.synchronize()
+        got[f"ov{t}"] = ov.cpu().numpy().copy()
+    upd, rd = res.kernel_times()
+    assert len(upd) == 2 and len(rd) == 2
+    for i in range(res.nlocal):
+        got[f"x{i}"] = res.get_state(i)
+    res.close()
+    return got
+
+
+def test_context_create_destroy_repeats(cuda):
+    """Eight contexts in one process, each taken through every lazy allocation, growth and
+    release (_lifetime_round) and destroyed: every round's outvecs, states and radius
+    enclosure are bitwise the first round's."""
+    import torch
+
+    ncu = torch.cuda.get_device_properties(cuda).multi_processor_count
+    first = _lifetime_round(cuda, ncu)
+    assert not any(np.isnan(v[:, :9]).any() for k, v in first.items() if k.startswith("ov"))
+    assert (first["lo"] <= first["hi"]).all() and (first["lo"] > 0).all()
+    for r in range(1, 8):
+        got = _lifetime_round(cuda, ncu)
+        assert sorted(got) == sorted(first)
+        for k in first:
+            np.testing.assert_array_equal(got[k], first[k], err_msg=f"round {r} {k}")
+
+
+# n / ninp per region, chunk_speedy, nout; what the context must report with begin mode 1
+# (step_shape's values, pinned on the CPU by tests/reservoir_layout_check.cpp)
+REPORTED = {
+    "n7168": dict(n=[7168, 2049], ninp=[64, 33], ncs=5, nout=9, balanced=True, fused=False),
+    "n7169": dict(n=[7169, 2], ninp=[33, 1], ncs=5, nout=9, balanced=False, fused=False),
+    "nout136": dict(n=[257, 257], ninp=[5, 33], ncs=7, nout=136, balanced=True, fused=True),
+    "nout137": dict(n=[257, 257], ninp=[5, 33], ncs=133, nout=137, balanced=True, fused=False),
+}
+
+
+@pytest.mark.parametrize("case", list(REPORTED))
+def test_reported_path_is_the_launched_path(cuda, case):
+    """On each side of the balanced update's edge (n 7168 / 7169) and of the fused
+    begin's (nout_pad 136 / 144): sml_res_update_balanced and sml_res_begin_fused report
+    the shape's value, and two begin + finish steps are bitwise those of the same context
+    with the per-region update forced and begin mode 0 -- so the form reported is a form
+    that ran, and it computes what the reference path computes."""
+    s = REPORTED[case]
+    ncs, nout, leak = s["ncs"], s["nout"], 1 / 3
+    ws = [_weights(n, p, ncs, nout, seed=i) for i, (n, p) in enumerate(zip(s["n"], s["ninp"]))]
+    fbs, lms = _series(ws, ncs, 2)
+    res = _generic(ws, ncs, nout, leak)
+    res.set_begin_mode(1)
+    assert res.update_balanced() == s["balanced"]
+    assert res.begin_fused == s["fused"]
+    seq = _run(res, fbs, lms, cuda, split=True)
+    ref = _generic(ws, ncs, nout, leak, per_region=True)
+    ref.set_begin_mode(0)
+    assert not ref.update_balanced() and not ref.begin_fused
+    _same(seq, _run(ref, fbs, lms, cuda, split=True), f"{case} against the reference paths")
+    assert not any(np.isnan(ov).any() for ov, _ in seq)
+
+
+@functools.lru_cache(maxsize=None)
+def _fresh_process_steps(tmp):
+    """_refused_create_child.py's two steps from a process that has done nothing else."""
+    import os
+    import subprocess
+    import sys
+
+    out = os.path.join(tmp, "fresh.npz")
+    child = os.path.join(os.path.dirname(os.path.abspath(__file__)), "_refused_create_child.py")
+    p = subprocess.run([sys.executable, "-u", child, out], timeout=100, capture_output=True, text=True)
+    assert p.returncode == 0, p.stdout[-3000:] + p.stderr[-3000:]
+    return dict(np.load(out))
+
+
+def test_refused_creates_leave_a_usable_process(cuda, tmp_path):
+    """A sml_train_create refused for naug[1] = 1 and a sml_res_create refused for a
+    region id out of range (each after the context object exists, so each takes the
+    bail-out), then a good create and one step of each: bitwise a fresh process's."""
+    import _refused_create_child as child
+    from speedy_ml_amd.training import Trainer
+
+    fresh = _fresh_process_steps(str(tmp_path))
+    with pytest.raises(SmlError, match=r"naug\[1\] = 1"):
+        Trainer([130, 1], child.TRAIN_NOUT)
+    np.testing.assert_array_equal(child.train_step(cuda), fresh["wout"])
+    with pytest.raises(SmlError, match="region id 1152 out of range"):
+        child.res_create(child.res_weights(), region_ids=(0, 1152))
+    ov, x0, x1 = child.res_step(cuda)
+    np.testing.assert_array_equal(ov, fresh["ov"])
+    np.testing.assert_array_equal(x0, fresh["x0"])
+    np.testing.assert_array_equal(x1, fresh["x1"])
+    assert not np.isnan(ov).any() and np.abs(fresh["wout"]).max() > 0

@@ -24,7 +24,14 @@ def test_reservoir_layout_check(tmp_path, variant):
     and an interior region -- n = 1, the overflow words' edges, every width 1..9, k = 0,
     duplicates, four W_in forms, fp32 / fp64 storage from both sources, and the rejected
     loads' messages.  (Blocks of one row, q = 1, have no 32-bit magic -- ceil(2^32 / 1)
-    wraps to 0 -- so the check pins that such a region keeps its stored columns.)"""
+    wraps to 0 -- so the check pins that such a region keeps its stored columns.)
+    Then step_shape (which kernel form each stage of a step takes, and its LDS) against
+    the predicates as the launchers spelt them, with their numbers written out: maxn 7168 /
+    7169, maxninp 1024 / 1025, the balanced and the drive LDS at max_lds (65536, 163840)
+    and one row over, the per-region LDS at 64 KiB and 8 bytes over, nout_pad 136 / 153 /
+    144, the grouped finish at ncs 133 / 134 / 0, nout_pad 144 / 148 and its switch, parts
+    at nlocal 1 / 512 / 513, every begin mode, each reference-path flag alone, and 6000
+    random inputs."""
     exe = tmp_path / ("reservoir_layout_check_" + variant)
     cmd = ["g++", "-std=gnu++17", "-ffp-contract=off", "-Wall", *VARIANTS[variant], "-I" + CSRC,
            os.path.join(HERE, "reservoir_layout_check.cpp"), os.path.join(CSRC, "sml_reservoir_layout.cpp"),
