@@ -324,6 +324,46 @@ int sml_res_footprint(const sml_reservoirs *c, int64_t *weight_bytes, int64_t *a
  * rearms the recorder. */
 int sml_res_enable_timing(sml_reservoirs *c, int capacity);
 int sml_res_kernel_times(sml_reservoirs *c, float *update_ms, float *readout_ms, int max_steps, int *count);
+/* Ensemble members: several states of every local region -- forecasts from perturbed
+ * initial conditions -- advanced through the same weights, which are then read once
+ * per step for a tile of members instead of once per member.
+ * sml_res_set_members: 1 .. SML_RES_MAX_MEMBERS members (1 at create: the context as it
+ * always was).  Member 0 keeps its state, the members kept on shrinking keep theirs,
+ * new members start from x = 0.  A set-up call (it waits for the device); SML_ERR_STATE
+ * inside a begun step, SML_ERR_ARG out of range.
+ * sml_res_set_state / _get_state are member 0 of the _member pair; setting a state
+ * discards a begun step.
+ * sml_res_step_members: sml_res_step for every member.  Member e's packed feedback is
+ * at d_feedback + e * fb_stride, its [nlocal][chunk_speedy] local model at
+ * d_local_model + e * lm_stride (ignored when chunk_speedy is 0), its [nlocal][ld]
+ * outvecs (ld: sml_res_set_outvec_ld) at d_outvec + e * ov_stride, strides in doubles;
+ * fb_stride >= the packed feedback size, lm_stride >= nlocal * chunk_speedy, ov_stride
+ * >= nlocal * ld, else SML_ERR_ARG.  Stream-ordered, no host synchronisation; every
+ * member advances in the one call.  The timing hook stamps it like sml_res_step.
+ * sml_res_synchronize_members: sml_res_synchronize for every member, block t of member
+ * e at d_inputs + t * stride + e * member_stride.
+ * For every member, outvecs and state are bit for bit those of sml_res_step
+ * (sml_res_synchronize) on a single-member context of the same weights started from
+ * that member's state and given that member's inputs.
+ * While the context holds more than one member, the single-member calls that advance
+ * the state -- sml_res_step, _step_begin, _step_slab, _synchronize, _start_prediction,
+ * _train_drive, _step_host -- return SML_ERR_STATE; sml_res_set_members(c, 1) makes
+ * them available again.
+ * sml_res_member_tile: the members one update block serves (bounded by the device's
+ * LDS where the region's state is staged there: update_lds 1) and the members one
+ * W_out load of the readout serves; W_out is streamed ceil(members / readout_tile)
+ * times per step. */
+#define SML_RES_MAX_MEMBERS 32
+int sml_res_set_members(sml_reservoirs *c, int members);
+int sml_res_members(const sml_reservoirs *c, int *members);
+int sml_res_set_state_member(sml_reservoirs *c, int member, int i, const double *x);
+int sml_res_get_state_member(sml_reservoirs *c, int member, int i, double *x);
+int sml_res_step_members(sml_reservoirs *c, const double *d_feedback, int64_t fb_stride,
+                         const double *d_local_model, int64_t lm_stride, double *d_outvec, int64_t ov_stride,
+                         void *stream);
+int sml_res_synchronize_members(sml_reservoirs *c, const double *d_inputs, int length, int64_t stride,
+                                int64_t member_stride, void *stream);
+int sml_res_member_tile(const sml_reservoirs *c, int *update_tile, int *update_lds, int *readout_tile);
 
 /* ------------------------------------------------------------- exchange/tiling */
 /* Global grids: d_grid4d[4*96*48*8], d_grid2d[96*48], d_precip[96*48].

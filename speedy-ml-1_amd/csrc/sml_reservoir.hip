@@ -54,6 +54,7 @@ SML_TL_DEFINE(reservoir)
 #include "sml_res_radius.hpp"
 #include "sml_res_tiling.hpp"
 #include "sml_res_readout.hpp"
+#include "sml_res_members.hpp"
 // clang-format on
 
 using namespace sml;
@@ -133,6 +134,11 @@ struct sml_reservoirs : PoolPlan {
     double *d_rad_xy = nullptr, *d_rad_part = nullptr;
     RadiusOut *d_rad_out = nullptr;
     StepShape shape;  // which form each stage takes, its LDS: what the launchers read and the ABI reports
+    // ensemble members (sml_res_set_members): member e's state at e * tot_xaug doubles of
+    // d_x[0] / d_x[1], so member 0 is the single-member context's state; mshape: the members
+    // kernels' tiles (member_shape), kept with the step's shape
+    int members = 1;
+    MemberShape mshape;
     int32_t *d_tgt_idx = nullptr;  // [nlocal][nout] the targets' positions in each region's feedback
     // the next grid finish waits in-kernel for *fin_wflag >= fin_wval (sml::res_finish_wait)
     const uint64_t *fin_wflag = nullptr;
@@ -251,6 +257,16 @@ void reshape(sml_reservoirs *c) {
         if (c->rd[i].a_w <= 0 || c->rd[i].w_w <= 0) ell_ok = false;
     c->shape = step_shape({c->maxn, c->maxninp, c->nout_pad, c->ncs, c->nlocal, c->max_lds, ell_ok, c->begin_mode,
                            c->per_region, c->finish_ungrouped, c->stepwise_drive});
+    c->mshape = member_shape({c->members, c->shape.lds_region, c->shape.region_lds, c->max_lds});
+}
+
+// the calls that advance one state through the single-member kernels: refused while the
+// context holds members, whose buffers they would move out from under the others
+int check_single(const sml_reservoirs *c, const char *what) {
+    if (c->members > 1)
+        return fail(SML_ERR_STATE, "%s on a context of %d members: call sml_res_set_members(c, 1) first", what,
+                    c->members);
+    return SML_OK;
 }
 
 // the exchange / tiling tables (build_region_tables): each allocated, then uploaded
@@ -614,6 +630,60 @@ void launch_finish_grid(sml_reservoirs *c, const double *d_fc4d, const double *d
     c->fin_wlate = nullptr;
 }
 
+// ---- ensemble members (sml_res_members.hpp): every member's update, then every member's
+// readout, each in one launch over tiles of members (c->mshape)
+int launch_update_mem(sml_reservoirs *c, const double *xo, double *xn, const double *d_feedback, int64_t fb_stride,
+                      hipStream_t st) {
+    const StepShape &s = c->shape;
+    const MemberShape &ms = c->mshape;
+    if (ms.update_tile < 1 || ms.update_tile > kMemberTile || ms.lds > c->max_lds)
+        return fail(SML_ERR_STATE, "the members update has no tile for this context (tile %d, %zu bytes of LDS)",
+                    ms.update_tile, ms.lds);
+    const int ntiles = (c->members + ms.update_tile - 1) / ms.update_tile;
+    const int nlog = s.parts * c->nlocal;
+    const Ell ell = make_ell(c);
+    const MemberArgs mem{c->members, ms.update_tile, c->tot_xaug, fb_stride, 0, 0};
+    with_wt(c, [&](auto tag) {
+        using WT = decltype(tag);
+        auto go = [&](auto kern) {
+            hipLaunchKernelGGL(kern, dim3(nlog * ntiles), dim3(kUpdThreads), ms.lds, st, c->d_rd, c->d_a_rp,
+                               c->d_a_col, (const WT *)c->d_a_val, c->d_w_rp, c->d_w_col, (const WT *)c->d_w_val, ell,
+                               xo, xn, d_feedback, c->leakage, s.parts, s.lds_x, s.lds_buf, ntiles, mem);
+        };
+        // (a tile of 3 or 4 only in a build with kMemberTile 4)
+        if (kMemberTile == 2 || ms.update_tile <= 2)
+            ms.update_lds ? go(k_res_update_mem<WT, true, 2>) : go(k_res_update_mem<WT, false, 2>);
+        else if constexpr (kMemberTile > 2)
+            ms.update_lds ? go(k_res_update_mem<WT, true, 4>) : go(k_res_update_mem<WT, false, 4>);
+    });
+    SML_HIP(hipGetLastError());
+    return SML_OK;
+}
+
+// xs: the state buffer the update just wrote (member e's x_aug rows at e * tot_xaug)
+int launch_readout_mem(sml_reservoirs *c, const double *xs, const double *d_local_model, int64_t lm_stride,
+                       double *d_outvec, int64_t ov_stride, hipStream_t st) {
+    const StepShape &s = c->shape;
+    const MemberShape &ms = c->mshape;
+    const int nitems = c->nlocal * s.groups, nwaves = nitems * ms.readout_streams;
+    const int nblocks = (nwaves + s.wpb - 1) / s.wpb;
+    const MemberArgs mem{c->members, ms.readout_tile, c->tot_xaug, 0, lm_stride, ov_stride};
+    with_wt(c, [&](auto tag) {
+        using WT = decltype(tag);
+        auto go = [&](auto kern) {
+            hipLaunchKernelGGL(kern, dim3(nblocks), dim3(64 * s.wpb), 0, st, c->d_rd, (const WT *)c->d_wout,
+                               (const WT *)c->d_wlm, xs, d_local_model, c->d_meanstd, c->d_outl, d_outvec, c->nout,
+                               c->ov_ld, c->nout_pad, c->ncs, s.groups, nitems, ms.readout_streams, mem);
+        };
+        if (kMemberTile == 2 || ms.readout_tile <= 2)
+            s.wide ? go(k_res_readout_mem<WT, kReadFull, kRowsWide, 2>) : go(k_res_readout_mem<WT, kReadFull, kRows, 2>);
+        else if constexpr (kMemberTile > 2)
+            s.wide ? go(k_res_readout_mem<WT, kReadFull, kRowsWide, 4>) : go(k_res_readout_mem<WT, kReadFull, kRows, 4>);
+    });
+    SML_HIP(hipGetLastError());
+    return SML_OK;
+}
+
 // the events of one timed step (sml_res_enable_timing), when the context has a free
 // slot: stamp(0) before the step, stamp(1) after the update, stamp(2) after the readout
 struct StepTimer {
@@ -720,20 +790,78 @@ extern "C" int sml_res_load_region_f64(sml_reservoirs *c, int i, const int *rows
     });
 }
 
-extern "C" int sml_res_set_state(sml_reservoirs *c, int i, const double *x) {
+extern "C" int sml_res_set_state_member(sml_reservoirs *c, int member, int i, const double *x) {
     if (int rc = check_region(c, i)) return rc;
+    SML_REQUIRE(member >= 0 && member < c->members, "member %d out of range [0,%d)", member, c->members);
     SML_REQUIRE(x, "x is null");
     // a begun step read the state being replaced: it is discarded (sml_res_step_cancel)
     if (int rc = sml_res_step_cancel(c)) return rc;
-    SML_HIP(hipMemcpy(c->x_now() + c->rd[i].x, x, (size_t)c->n[i] * 8, hipMemcpyHostToDevice));
+    SML_HIP(hipMemcpy(c->x_now() + (size_t)member * c->tot_xaug + c->rd[i].x, x, (size_t)c->n[i] * 8,
+                      hipMemcpyHostToDevice));
     return SML_OK;
 }
 
-extern "C" int sml_res_get_state(sml_reservoirs *c, int i, double *x) {
+extern "C" int sml_res_get_state_member(sml_reservoirs *c, int member, int i, double *x) {
     if (int rc = check_region(c, i)) return rc;
+    SML_REQUIRE(member >= 0 && member < c->members, "member %d out of range [0,%d)", member, c->members);
     SML_REQUIRE(x, "x is null");
     SML_HIP(hipDeviceSynchronize());
-    SML_HIP(hipMemcpy(x, c->x_now() + c->rd[i].x, (size_t)c->n[i] * 8, hipMemcpyDeviceToHost));
+    SML_HIP(hipMemcpy(x, c->x_now() + (size_t)member * c->tot_xaug + c->rd[i].x, (size_t)c->n[i] * 8,
+                      hipMemcpyDeviceToHost));
+    return SML_OK;
+}
+
+extern "C" int sml_res_set_state(sml_reservoirs *c, int i, const double *x) {
+    return sml_res_set_state_member(c, 0, i, x);
+}
+
+extern "C" int sml_res_get_state(sml_reservoirs *c, int i, double *x) { return sml_res_get_state_member(c, 0, i, x); }
+
+// The number of members (1 .. SML_RES_MAX_MEMBERS; 1 at create).  Both state buffers are
+// laid out anew, filled with zeros: the members kept (member 0 always) are copied over,
+// new members start from x = 0 with zero row padding, which the readout's 16-byte loads
+// run over.  A set-up call: it waits for the device.
+extern "C" int sml_res_set_members(sml_reservoirs *c, int members) {
+    SML_REQUIRE(c, "null context");
+    SML_REQUIRE(members >= 1 && members <= kMaxMembers, "members %d outside 1..%d", members, kMaxMembers);
+    if (c->is_begun()) return fail(SML_ERR_STATE, "sml_res_set_members inside a begun step");
+    if (members == c->members) return SML_OK;
+    SML_HIP(hipDeviceSynchronize());  // steps in flight read the old buffers
+    const int64_t keep = (int64_t)std::min(members, c->members) * c->tot_xaug;
+    double *nx[2] = {nullptr, nullptr};
+    pool(c, &nx[0], (int64_t)members * c->tot_xaug, true);
+    pool(c, &nx[1], (int64_t)members * c->tot_xaug, true);
+    hipError_t e = hipSuccess;
+    for (int q = 0; q < 2 && c->mem.status() == SML_OK && e == hipSuccess && keep > 0; ++q)
+        e = hipMemcpy(nx[q], c->d_x[q], (size_t)keep * 8, hipMemcpyDeviceToDevice);
+    if (c->mem.status() != SML_OK || e != hipSuccess) {
+        c->mem.release(&nx[0]);
+        c->mem.release(&nx[1]);
+        return c->mem.status() ? c->mem.status()
+                               : fail(SML_ERR_HIP, "sml_res_set_members: %s", hipGetErrorString(e));
+    }
+    for (int q = 0; q < 2; ++q) {
+        c->mem.release(&c->d_x[q]);
+        c->d_x[q] = nx[q];
+    }
+    c->members = members;
+    reshape(c);
+    return SML_OK;
+}
+
+extern "C" int sml_res_members(const sml_reservoirs *c, int *members) {
+    SML_REQUIRE(c && members, "null argument");
+    *members = c->members;
+    return SML_OK;
+}
+
+// the tiles the members kernels run with (member_shape): members per update block, whether
+// their x and u are staged in LDS, members per W_out load of the readout
+extern "C" int sml_res_member_tile(const sml_reservoirs *c, int *update_tile, int *update_lds, int *readout_tile) {
+    SML_REQUIRE(c && update_tile && update_lds && readout_tile, "null argument");
+    *update_tile = c->mshape.update_tile;
+    *update_lds = c->mshape.update_lds ? 1 : 0;
+    *readout_tile = c->mshape.readout_tile;
     return SML_OK;
 }
 
@@ -850,6 +978,7 @@ extern "C" int sml_res_kernel_times(sml_reservoirs *c, float *update_ms, float *
 
 extern "C" int sml_res_step_begin(sml_reservoirs *c, const double *d_feedback, void *stream) {
     SML_REQUIRE(c, "null context");
+    if (int rc = check_single(c, "sml_res_step_begin")) return rc;
     if (c->nlocal == 0) return SML_OK;
     SML_REQUIRE(d_feedback, "null device buffer");
     if (c->is_begun()) return fail(SML_ERR_STATE, "sml_res_step_begin called twice without sml_res_step_finish");
@@ -910,6 +1039,7 @@ extern "C" int sml_res_step_finish(sml_reservoirs *c, const double *d_local_mode
 extern "C" int sml_res_step_slab(sml_reservoirs *c, const double *d_feedback, const double *d_local_model,
                                  double *d_local_model_next, double *d_outvec, void *stream) {
     SML_REQUIRE(c, "null context");
+    if (int rc = check_single(c, "sml_res_step_slab")) return rc;
     if (c->nlocal == 0) return SML_OK;
     SML_REQUIRE(d_feedback && d_outvec && d_local_model_next && (c->ncs == 0 || d_local_model), "null device buffer");
     SML_REQUIRE(d_local_model_next != d_local_model, "d_local_model_next must not alias d_local_model");
@@ -975,6 +1105,7 @@ extern "C" int sml_res_step_finish_assemble(sml_reservoirs *c, const double *d_f
 extern "C" int sml_res_step(sml_reservoirs *c, const double *d_feedback, const double *d_local_model,
                             double *d_outvec, void *stream) {
     SML_REQUIRE(c, "null context");
+    if (int rc = check_single(c, "sml_res_step")) return rc;
     if (c->nlocal == 0) return SML_OK;
     SML_REQUIRE(d_feedback && d_outvec, "null device buffer");
     SML_REQUIRE(c->ncs == 0 || d_local_model, "hybrid context needs d_local_model");
@@ -999,6 +1130,7 @@ extern "C" int sml_res_step(sml_reservoirs *c, const double *d_feedback, const d
 extern "C" int sml_res_synchronize(sml_reservoirs *c, const double *d_inputs, int length, int64_t stride,
                                    void *stream) {
     SML_REQUIRE(c && length >= 0, "bad argument");
+    if (int rc = check_single(c, "sml_res_synchronize")) return rc;
     if (c->nlocal == 0 || length == 0) return SML_OK;
     SML_REQUIRE(d_inputs && stride >= (int64_t)c->tot_fb, "stride smaller than the packed feedback size");
     if (c->is_begun()) return fail(SML_ERR_STATE, "sml_res_synchronize inside a begun step");
@@ -1012,12 +1144,76 @@ extern "C" int sml_res_synchronize(sml_reservoirs *c, const double *d_inputs, in
     return SML_OK;
 }
 
+// sml_res_step for every member of the context in one stream of the weights: member e's
+// feedback, local model and outvecs at e * fb_stride / lm_stride / ov_stride doubles.
+// One member takes sml_res_step's own kernels.  All members advance together: one swap.
+extern "C" int sml_res_step_members(sml_reservoirs *c, const double *d_feedback, int64_t fb_stride,
+                                    const double *d_local_model, int64_t lm_stride, double *d_outvec,
+                                    int64_t ov_stride, void *stream) {
+    SML_REQUIRE(c, "null context");
+    if (c->nlocal == 0) return SML_OK;
+    SML_REQUIRE(d_feedback && d_outvec, "null device buffer");
+    SML_REQUIRE(c->ncs == 0 || d_local_model, "hybrid context needs d_local_model");
+    SML_REQUIRE(fb_stride >= c->tot_fb, "fb_stride %lld smaller than the packed feedback size %lld",
+                (long long)fb_stride, (long long)c->tot_fb);
+    SML_REQUIRE(c->ncs == 0 || lm_stride >= (int64_t)c->nlocal * c->ncs,
+                "lm_stride %lld smaller than nlocal * chunk_speedy", (long long)lm_stride);
+    SML_REQUIRE(ov_stride >= (int64_t)c->nlocal * c->ov_ld, "ov_stride %lld smaller than nlocal * the outvec row stride",
+                (long long)ov_stride);
+    if (c->is_begun()) return fail(SML_ERR_STATE, "sml_res_step_members inside a begun step");
+    if (int rc = check_loaded(c)) return rc;
+    if (c->ncs == 0) {
+        d_local_model = nullptr;
+        lm_stride = 0;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    return c->advance(false, [&](const double *xo, double *xn) {
+        StepTimer timer(c, st);
+        if (int rc = timer.stamp(0)) return rc;
+        if (c->members == 1) {
+            if (int rc = launch_update(c, xo, xn, d_feedback, st)) return rc;
+            if (int rc = timer.stamp(1)) return rc;
+            launch_readout<kReadFull>(c, xn, d_local_model, d_outvec, st);
+            SML_HIP(hipGetLastError());
+        } else {
+            if (int rc = launch_update_mem(c, xo, xn, d_feedback, fb_stride, st)) return rc;
+            if (int rc = timer.stamp(1)) return rc;
+            if (int rc = launch_readout_mem(c, xn, d_local_model, lm_stride, d_outvec, ov_stride, st)) return rc;
+        }
+        return timer.stamp(2);
+    });
+}
+
+// sml_res_synchronize for every member: block t of member e at d_inputs + t * stride +
+// e * member_stride doubles
+extern "C" int sml_res_synchronize_members(sml_reservoirs *c, const double *d_inputs, int length, int64_t stride,
+                                           int64_t member_stride, void *stream) {
+    SML_REQUIRE(c && length >= 0, "bad argument");
+    if (c->nlocal == 0 || length == 0) return SML_OK;
+    SML_REQUIRE(d_inputs && stride >= (int64_t)c->tot_fb, "stride smaller than the packed feedback size");
+    SML_REQUIRE(c->members == 1 || member_stride >= (int64_t)c->tot_fb,
+                "member_stride smaller than the packed feedback size");
+    if (c->is_begun()) return fail(SML_ERR_STATE, "sml_res_synchronize_members inside a begun step");
+    if (int rc = check_loaded(c)) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    for (int t = 0; t < length; ++t) {
+        const double *u = d_inputs + (size_t)t * stride;
+        if (int rc = c->advance(false, [&](const double *xo, double *xn) {
+                return c->members == 1 ? launch_update(c, xo, xn, u, st)
+                                       : launch_update_mem(c, xo, xn, u, member_stride, st);
+            }))
+            return rc;
+    }
+    return SML_OK;
+}
+
 // the training drive (k_res_drive): "record, then advance" over one batch of m
 // columns for every local region.  Stream-ordered, no host synchronisation.
 extern "C" int sml_res_train_drive(sml_reservoirs *c, const double *d_inputs, int m, int64_t stride,
                                    const double *d_model, int64_t model_stride, double *d_states,
                                    double *d_targets, void *stream) {
     SML_REQUIRE(c && m >= 0, "bad argument");
+    if (int rc = check_single(c, "sml_res_train_drive")) return rc;
     if (c->nlocal == 0 || m == 0) return SML_OK;
     SML_REQUIRE(d_inputs && stride >= (int64_t)c->tot_fb, "stride smaller than the packed feedback size");
     SML_REQUIRE(d_states, "null device buffer");
@@ -1123,6 +1319,7 @@ extern "C" int sml_res_spectral_radius(sml_reservoirs *c, double tol, int max_it
 extern "C" int sml_res_start_prediction(sml_reservoirs *c, const double *d_inputs, int length, int64_t stride,
                                         double *d_feedback, void *stream) {
     SML_REQUIRE(c && d_inputs && d_feedback && length >= 0, "bad argument");
+    if (int rc = check_single(c, "sml_res_start_prediction")) return rc;
     if (int rc = sml_res_synchronize(c, d_inputs, length, stride, stream)) return rc;
     if (c->tot_fb)
         SML_HIP(hipMemcpyAsync(d_feedback, d_inputs + (size_t)length * stride, (size_t)c->tot_fb * 8,
@@ -1134,6 +1331,7 @@ extern "C" int sml_res_step_host(sml_reservoirs *c, const double *feedback, cons
                                  double *outvec) {
     SML_REQUIRE(c && feedback && outvec, "null argument");
     SML_REQUIRE(c->ncs == 0 || local_model, "hybrid context needs local_model");
+    if (int rc = check_single(c, "sml_res_step_host")) return rc;
     const size_t nfb = c->tot_fb, nlm = (size_t)c->nlocal * c->ncs, nov = (size_t)c->nlocal * c->ov_ld;
     if (c->d_io_n != nfb + nlm + nov) {  // sized for the current outvec stride
         c->mem.release(&c->d_io);

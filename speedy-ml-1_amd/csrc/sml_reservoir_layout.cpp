@@ -94,6 +94,20 @@ StepShape step_shape(const StepShapeIn &in) {
     return s;
 }
 
+MemberShape member_shape(const MemberShapeIn &in) {
+    MemberShape m;
+    m.update_lds = in.region_lds;
+    m.update_tile = std::min(in.members, kMemberTile);
+    // staged: the tile's x and u side by side within the device's LDS per workgroup
+    // (an empty context stages nothing: no bound)
+    if (m.update_lds && in.lds_region > 0)
+        m.update_tile = (int)std::min<size_t>((size_t)m.update_tile, in.max_lds / in.lds_region);
+    m.lds = m.update_lds ? (size_t)m.update_tile * in.lds_region : 0;
+    m.readout_tile = std::min(in.members, kMemberTile);
+    m.readout_streams = (in.members + m.readout_tile - 1) / m.readout_tile;
+    return m;
+}
+
 template <typename SrcT, typename StoT>
 int pack_region(const PackIn &in, const RegionDev &rg, const int *rows, const int *cols, const SrcT *vals,
                 const SrcT *win, const SrcT *wout, PackedRegion<StoT> *out) {

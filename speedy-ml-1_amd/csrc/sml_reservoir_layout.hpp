@@ -117,6 +117,35 @@ struct StepShape {
 
 StepShape step_shape(const StepShapeIn &in);
 
+// ------------------------------------------------------------------ ensemble members
+// Members (sml_res_set_members): E states advance through one stream of the weights.
+// A members kernel (sml_res_members.hpp) serves a tile of members per block (update) or
+// per wave (readout); members beyond one tile run as further tiles, each of which reads
+// the weights again.
+#ifndef SML_MEMBER_TILE
+#define SML_MEMBER_TILE 2  // 2 or 4 (profiles/members.md: 4 x 17 sums a wave do not fit the registers)
+#endif
+constexpr int kMemberTile = SML_MEMBER_TILE;
+static_assert(kMemberTile == 2 || kMemberTile == 4, "the members kernels are built for tiles of 2 and 4");
+constexpr int kMaxMembers = 32;  // SML_RES_MAX_MEMBERS
+
+struct MemberShapeIn {
+    int members;
+    size_t lds_region;  // StepShape::lds_region: x and u of the largest region, one member
+    bool region_lds;    // StepShape::region_lds: the per-region update stages in LDS
+    size_t max_lds;     // the device's LDS per workgroup
+};
+
+struct MemberShape {
+    int update_tile;      // members a block of k_res_update_mem serves
+    bool update_lds;      // their x and u staged side by side in LDS (else gathered from global memory)
+    size_t lds;           // the block's LDS: update_tile staging buffers
+    int readout_tile;     // members a wave of k_res_readout_mem serves per W_out load
+    int readout_streams;  // times W_out is streamed per step: ceil(members / readout_tile)
+};
+
+MemberShape member_shape(const MemberShapeIn &in);
+
 // ------------------------------------------------------------------ one region's weights
 // what sml_res_load_region uploads, in the storage dtype: A and W_in as CSR, W_out
 // transposed and padded (wt [nout_pad][ld]) with its local-model block (wl [ncs][nout_pad]),

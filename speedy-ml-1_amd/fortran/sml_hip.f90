@@ -161,6 +161,57 @@ module sml_hip
       integer(c_int) :: rc
     end function
 
+    ! ensemble members: several states of every region through one stream of the weights
+    ! (member, i 0-based; strides in doubles; per member bitwise sml_res_step / _synchronize)
+    function sml_res_set_members(ctx, members) bind(C, name='sml_res_set_members') result(rc)
+      import :: c_ptr, c_int
+      type(c_ptr), value :: ctx
+      integer(c_int), value :: members
+      integer(c_int) :: rc
+    end function
+    function sml_res_members(ctx, members) bind(C, name='sml_res_members') result(rc)
+      import :: c_ptr, c_int
+      type(c_ptr), value :: ctx
+      integer(c_int), intent(out) :: members
+      integer(c_int) :: rc
+    end function
+    function sml_res_set_state_member(ctx, member, i, x) bind(C, name='sml_res_set_state_member') result(rc)
+      import :: c_ptr, c_int, c_double
+      type(c_ptr), value :: ctx
+      integer(c_int), value :: member, i
+      real(c_double), intent(in) :: x(*)
+      integer(c_int) :: rc
+    end function
+    function sml_res_get_state_member(ctx, member, i, x) bind(C, name='sml_res_get_state_member') result(rc)
+      import :: c_ptr, c_int, c_double
+      type(c_ptr), value :: ctx
+      integer(c_int), value :: member, i
+      real(c_double), intent(out) :: x(*)
+      integer(c_int) :: rc
+    end function
+    function sml_res_step_members(ctx, d_feedback, fb_stride, d_local_model, lm_stride, d_outvec, ov_stride, &
+        stream) bind(C, name='sml_res_step_members') result(rc)
+      import :: c_ptr, c_int, c_int64_t
+      type(c_ptr), value :: ctx, d_feedback, d_local_model, d_outvec, stream
+      integer(c_int64_t), value :: fb_stride, lm_stride, ov_stride
+      integer(c_int) :: rc
+    end function
+    function sml_res_synchronize_members(ctx, d_inputs, length, stride, member_stride, stream) &
+        bind(C, name='sml_res_synchronize_members') result(rc)
+      import :: c_ptr, c_int, c_int64_t
+      type(c_ptr), value :: ctx, d_inputs, stream
+      integer(c_int), value :: length
+      integer(c_int64_t), value :: stride, member_stride
+      integer(c_int) :: rc
+    end function
+    function sml_res_member_tile(ctx, update_tile, update_lds, readout_tile) bind(C, name='sml_res_member_tile') &
+        result(rc)
+      import :: c_ptr, c_int
+      type(c_ptr), value :: ctx
+      integer(c_int), intent(out) :: update_tile, update_lds, readout_tile
+      integer(c_int) :: rc
+    end function
+
     ! predict split at column chunk_size_speedy (v_ml + v_p, mod_reservoir.f90:1456-1459)
     function sml_res_step_begin(ctx, d_feedback, stream) bind(C, name='sml_res_step_begin') result(rc)
       import :: c_ptr, c_int

@@ -65,6 +65,8 @@ EXPORTED = (
     "sml_dyn_set_check_timeout", "sml_dyn_check_stream", "sml_dyn_set_fused", "sml_res_set_reference_paths",
     "sml_train_set_panel", "sml_res_train_drive", "sml_region_target_index",
     "sml_res_spectral_radius", "sml_gen_region",
+    "sml_res_set_members", "sml_res_members", "sml_res_set_state_member", "sml_res_get_state_member",
+    "sml_res_step_members", "sml_res_synchronize_members", "sml_res_member_tile",
 )
 
 SML_HOP_AUTO, SML_HOP_WAIT_VALUE, SML_HOP_EVENTS, SML_HOP_KERNEL = 0, 1, 2, 3
@@ -273,6 +275,13 @@ def _declare(L: ctypes.CDLL) -> None:
         "sml_region_target_index": [i, i, i, vp, ip],
         "sml_res_spectral_radius": [vp, d, i, vp, vp, vp, vp, vp],
         "sml_gen_region": [i, i, i, ctypes.c_uint64, i, d, vp, vp, vp, vp, vp],
+        "sml_res_set_members": [vp, i],
+        "sml_res_members": [vp, ip],
+        "sml_res_set_state_member": [vp, i, i, vp],
+        "sml_res_get_state_member": [vp, i, i, vp],
+        "sml_res_step_members": [vp, vp, ctypes.c_int64, vp, ctypes.c_int64, vp, ctypes.c_int64, vp],
+        "sml_res_synchronize_members": [vp, vp, i, ctypes.c_int64, ctypes.c_int64, vp],
+        "sml_res_member_tile": [vp, ip, ip, ip],
     }
     for name, args in sig.items():
         if os.environ.get("SML_LIB") and not hasattr(L, name):

@@ -49,6 +49,7 @@ class Reservoirs:
                                                ptr(self.n), ptr(self.k), chunk_speedy, nout, ptr(self._oidx), dt,
                                                leakage, ctypes.byref(h)))
         self._h = h
+        self._ov_ld = nout  # the outvec row stride (set_outvec_ld)
         off = np.zeros(self.nlocal + 1, dtype=np.int64)
         check(lib().sml_res_feedback_offsets(self._h, ptr(off)))
         self.fb_offsets = off
@@ -93,14 +94,99 @@ class Reservoirs:
         self.load_region(i, d["rows"], d["cols"], d["vals"], d["win"], d["wout"],
                          d["mean"].astype(np.float64), d["std"].astype(np.float64))
 
-    def set_state(self, i: int, x):
+    def set_state(self, i: int, x, member: int = 0):
         x = np.ascontiguousarray(x, dtype=np.float64)
-        check(lib().sml_res_set_state(self._h, i, ptr(x)))
+        if member == 0:  # (the entry point every build of the library has: SML_LIB A/B runs)
+            check(lib().sml_res_set_state(self._h, i, ptr(x)))
+        else:
+            check(lib().sml_res_set_state_member(self._h, int(member), i, ptr(x)))
 
-    def get_state(self, i: int) -> np.ndarray:
+    def get_state(self, i: int, member: int = 0) -> np.ndarray:
         x = np.zeros(int(self.n[i]))
-        check(lib().sml_res_get_state(self._h, i, ptr(x)))
+        if member == 0:
+            check(lib().sml_res_get_state(self._h, i, ptr(x)))
+        else:
+            check(lib().sml_res_get_state_member(self._h, int(member), i, ptr(x)))
         return x
+
+    # --- ensemble members
+    def set_members(self, members: int):
+        """The number of ensemble members (sml_res_set_members; 1 at create): states of
+        every region that advance through the same weights.  Member 0 keeps its state,
+        new members start from x = 0.  While members > 1 the single-member calls that
+        advance the state (predict, predict_begin, synchronize, ...) are refused."""
+        check(lib().sml_res_set_members(self._h, int(members)))
+
+    @property
+    def members(self) -> int:
+        v = ctypes.c_int()
+        check(lib().sml_res_members(self._h, ctypes.byref(v)))
+        return v.value
+
+    def member_tile(self) -> dict:
+        """The tiles the members kernels run with (sml_res_member_tile): members per
+        update block, whether their states are staged in LDS, members per W_out load."""
+        v = [ctypes.c_int() for _ in range(3)]
+        check(lib().sml_res_member_tile(self._h, *[ctypes.byref(x) for x in v]))
+        return dict(update_tile=v[0].value, update_lds=bool(v[1].value), readout_tile=v[2].value)
+
+    @staticmethod
+    def _member_rows(t, what, shape, row_min):
+        """A float64 device tensor [shape..., >= row_min] whose trailing dimensions are
+        dense (a member's block is what the library lays out): its leading stride."""
+        import torch
+
+        if t.dtype != torch.float64 or not t.is_cuda:
+            raise ValueError(f"{what}: a float64 device tensor expected")
+        if t.dim() != len(shape) + 1 or tuple(t.shape[:-1]) != tuple(shape) or t.shape[-1] < row_min:
+            raise ValueError(f"{what}: shape {tuple(shape)} + (>= {row_min},) expected, got {tuple(t.shape)}")
+        want = 1
+        for d in range(t.dim() - 1, 0, -1):  # every dimension but the first is packed
+            if t.shape[d] != 1 and t.stride(d) != want:
+                raise ValueError(f"{what}: only the first dimension may be strided, got strides {t.stride()}")
+            want *= t.shape[d]
+        if t.shape[0] > 1 and t.stride(0) < want:
+            raise ValueError(f"{what}: the first dimension's stride {t.stride(0)} is below {want}")
+        return int(t.stride(0)) if t.shape[0] > 1 else want
+
+    def predict_members(self, d_feedback, d_local_model, d_outvec, stream=None):
+        """predict for every member in one stream of the weights (sml_res_step_members):
+        d_feedback [E, >= total feedback], d_local_model [E, nlocal, chunk_speedy] (None
+        when chunk_speedy == 0), d_outvec [E, nlocal, the outvec row stride].  Member e's
+        outvecs and state are bitwise those of predict on a context of its own."""
+        E = self.members
+        fbs = self._member_rows(d_feedback, "d_feedback", (E,), int(self.fb_offsets[-1]))
+        lms = 0
+        if self.ncs:
+            if d_local_model is None:
+                raise ValueError("d_local_model: a hybrid context needs it")
+            lms = self._member_rows(d_local_model, "d_local_model", (E, self.nlocal), self.ncs)
+            if d_local_model.shape[-1] != self.ncs:
+                raise ValueError(f"d_local_model: rows of {self.ncs} doubles expected")
+        ovs = self._member_rows(d_outvec, "d_outvec", (E, self.nlocal), self._ov_ld)
+        if d_outvec.shape[-1] != self._ov_ld:
+            raise ValueError(f"d_outvec: rows of {self._ov_ld} doubles expected (set_outvec_ld)")
+        check(lib().sml_res_step_members(self._h, ptr(d_feedback), fbs, ptr(d_local_model if self.ncs else None), lms,
+                                         ptr(d_outvec), ovs, stream_ptr(stream)))
+
+    def synchronize_members(self, d_inputs, length: int, stream=None):
+        """synchronize for every member (sml_res_synchronize_members): d_inputs
+        [>= length, E, >= total feedback]; `length` updates of every member, no readout."""
+        import torch
+
+        E, tot = self.members, int(self.fb_offsets[-1])
+        if d_inputs.dtype != torch.float64 or not d_inputs.is_cuda:
+            raise ValueError("d_inputs: a float64 device tensor expected")
+        if d_inputs.dim() != 3 or d_inputs.shape[0] < length or d_inputs.shape[1] != E or d_inputs.shape[2] < tot:
+            raise ValueError(f"d_inputs: shape (>= {length}, {E}, >= {tot}) expected, got {tuple(d_inputs.shape)}")
+        if d_inputs.shape[2] > 1 and d_inputs.stride(2) != 1:
+            raise ValueError("d_inputs: a member's block must be packed")
+        stride = int(d_inputs.stride(0)) if d_inputs.shape[0] > 1 else E * max(int(d_inputs.stride(1)), tot)
+        mstride = int(d_inputs.stride(1)) if E > 1 else tot
+        if mstride < tot or stride < tot:
+            raise ValueError(f"d_inputs: strides {d_inputs.stride()} below the packed feedback size {tot}")
+        check(lib().sml_res_synchronize_members(self._h, ptr(d_inputs), int(length), stride, mstride,
+                                                stream_ptr(stream)))
 
     # --- device buffers
     def alloc_io(self, device="cuda"):
@@ -139,6 +225,7 @@ class Reservoirs:
     def set_outvec_ld(self, ld: int):
         """Row stride (>= nout) of the outvec arrays the context writes (sml_res_set_outvec_ld)."""
         check(lib().sml_res_set_outvec_ld(self._h, int(ld)))
+        self._ov_ld = int(ld)
 
     def set_update_cus(self, cus: int):
         """The CUs this context's launches get (sml_res_set_update_cus; 0 = the device)."""
