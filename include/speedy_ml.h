@@ -364,6 +364,45 @@ int sml_res_step_members(sml_reservoirs *c, const double *d_feedback, int64_t fb
 int sml_res_synchronize_members(sml_reservoirs *c, const double *d_inputs, int length, int64_t stride,
                                 int64_t member_stride, void *stream);
 int sml_res_member_tile(const sml_reservoirs *c, int *update_tile, int *update_lds, int *readout_tile);
+/* The split step for every member: sml_res_step_begin / _finish / _finish_grid /
+ * _finish_assemble with a member dimension, so that an E-member hybrid forecast runs its
+ * update and v_ml (about 98 % of the bytes) beside SPEEDY's windows and only the v_p finish
+ * behind them.  Member e's data is at e * stride doubles of each array, as in
+ * sml_res_step_members; every stride is checked against its packed size (SML_ERR_ARG naming
+ * it): fb_stride, lm_stride, ov_stride as there, the forecast and grid strides >= 8*48*96*4
+ * (fc4_stride, g4_stride) and >= 48*96 (fc2_stride, g2_stride: logp, and precip with it).
+ * sml_res_step_begin_members: every member's update, then every member's v_ml into
+ * context-owned partial sums (laid out by sml_res_set_members); two launches; the v_ml
+ * launch honours sml_res_set_read_waves as a cap on its waves.  All members advance
+ * together: one sml_res_step_cancel rolls all of them back, sml_res_step_begun reports
+ * the step, sml_res_set_state_member discards it; sml_res_set_members, _step_members and
+ * _synchronize_members inside it return SML_ERR_STATE.
+ * sml_res_step_finish_members: per member v_p + v_ml from that member's local model,
+ * unstandardized.  sml_res_step_finish_grid_members: each member's local model is first
+ * tiled and standardized from that member's forecast grids (and written to d_local_model
+ * when given), one block per (region, tile of members): sml_res_member_finish_tile
+ * reports the tile (1 at more than one member: the single-member kernel once per member).
+ * sml_res_step_finish_assemble_members also scatters each member's outputs into that
+ * member's grids with the root's clips (every region on this rank, in global order).
+ * None of them waits in-kernel for a forecast: order the stream behind the windows.
+ * For every member, outvecs, local models, grids and state are bit for bit those of the
+ * single-member calls on a context of its own.  At one member the four calls are the
+ * single-member calls (the same kernels, the fused begin where the shape takes it) and
+ * pair freely with them.  At more than one member sml_res_step_begin keeps refusing, and
+ * the single-member finishes return SML_ERR_STATE and leave the step begun. */
+int sml_res_step_begin_members(sml_reservoirs *c, const double *d_feedback, int64_t fb_stride, void *stream);
+int sml_res_step_finish_members(sml_reservoirs *c, const double *d_local_model, int64_t lm_stride,
+                                double *d_outvec, int64_t ov_stride, void *stream);
+int sml_res_step_finish_grid_members(sml_reservoirs *c, const double *d_fc4d, int64_t fc4_stride,
+                                     const double *d_fc2d, int64_t fc2_stride,
+                                     double *d_local_model /* may be NULL */, int64_t lm_stride, double *d_outvec,
+                                     int64_t ov_stride, void *stream);
+int sml_res_step_finish_assemble_members(sml_reservoirs *c, const double *d_fc4d, int64_t fc4_stride,
+                                         const double *d_fc2d, int64_t fc2_stride,
+                                         double *d_local_model /* may be NULL */, int64_t lm_stride,
+                                         double *d_outvec, int64_t ov_stride, double *d_grid4d, int64_t g4_stride,
+                                         double *d_grid2d, double *d_precip, int64_t g2_stride, void *stream);
+int sml_res_member_finish_tile(const sml_reservoirs *c, int *finish_tile);
 
 /* ------------------------------------------------------------- exchange/tiling */
 /* Global grids: d_grid4d[4*96*48*8], d_grid2d[96*48], d_precip[96*48].

@@ -9,6 +9,10 @@
 // the update; for the readout the same lanes, columns, per-lane fma order and butterfly
 // as rows_dot, then vp_sum and unstd -- so every member's bits are those of sml_res_step
 // on a context of its own.
+// The split step: k_res_readout_mem's kReadML form leaves every member's v_ml in the
+// context's partial sums (sml_res_step_begin_members); k_res_finish_mem and
+// k_res_finish_grid_mem are k_res_finish and k_res_finish_grid with a member dimension, the
+// latter a block per (region, tile of members) whose gathers fly together.
 // (A timeline build, SML_TL, needs the unit's SML_TL_DEFINE ahead of this header.)
 #pragma once
 #include <hip/hip_runtime.h>
@@ -25,10 +29,10 @@ using namespace sml;
 
 // what locates the members of a launch: E members, `tile` of them per block / wave,
 // member e's state at e * xs, feedback at e * fbs, local model at e * lms, outvecs at
-// e * ovs (doubles)
+// e * ovs, the v_ml partial sums of a begun step at e * ps (doubles)
 struct MemberArgs {
     int members, tile;
-    int64_t xs, fbs, lms, ovs;
+    int64_t xs, fbs, lms, ovs, ps;
 };
 
 // logical block = (region, part, tile of members): the tiles of one (region, part) are
@@ -155,15 +159,24 @@ __device__ __attribute__((always_inline)) inline RowsMem<R, T> rows_dot_mem(cons
 // W_out rows a later stream reads again are the ones its neighbour wave is reading).
 // T: the compile-time bound of the tile (mem.tile <= T).  The slots of a tile past its
 // members read member E - 1's x and write nothing.
+// kReadML (sml_res_step_begin_members): v_ml alone, as k_res_readout<kReadML> leaves it --
+// lane 0 writes the tile's T x NR sums into their members' partial-sum rows ([nlocal][nout_pad]
+// at e * mem.ps); no v_p, no outvec.  Without the epilogue's registers the compiler takes
+// the 17-row form to 162 VGPRs for three waves per SIMD and keeps one pass of loads in
+// flight; held to two waves per SIMD, as the one-pass form runs, it uses 210 / 248 (fp32 /
+// fp64 storage) and the begin is a quarter faster (profiles/members.md).  The other forms
+// keep the compiler's default range (1 .. 8).
 template <typename WT, int kMode, int NR, int T>
-__global__ __launch_bounds__(512) void k_res_readout_mem(const RegionDev *__restrict__ R, const WT *__restrict__ wout,
+__global__ __launch_bounds__(512)
+__attribute__((amdgpu_waves_per_eu(kMode == kReadML && NR == kRowsWide ? 2 : 1,
+                                   kMode == kReadML && NR == kRowsWide ? 2 : 8))) void k_res_readout_mem(const RegionDev *__restrict__ R, const WT *__restrict__ wout,
                                                          const WT *__restrict__ wlm, const double *__restrict__ xst,
                                                          const double *__restrict__ local_model,
                                                          const double *__restrict__ meanstd,
-                                                         const int8_t *__restrict__ outl, double *__restrict__ outvec,
-                                                         int nout, int ov_ld, int nout_pad, int ncs, int groups,
+                                                         const int8_t *__restrict__ outl, double *__restrict__ part,
+                                                         double *__restrict__ outvec, int nout, int ov_ld, int nout_pad, int ncs, int groups,
                                                          int nitems, int nstreams, MemberArgs mem) {
-    static_assert(kMode == kReadFull, "members advance in one pass (sml_res_step_members)");
+    static_assert(kMode == kReadFull || kMode == kReadML, "the members readout is the one pass or the v_ml half");
     SML_TL_SCOPE(sml::tl::kReadout);
     const int bs = xcd_remap(blockIdx.x, gridDim.x);
     const int lane = threadIdx.x & 63;
@@ -183,9 +196,22 @@ __global__ __launch_bounds__(512) void k_res_readout_mem(const RegionDev *__rest
         const RowsMem<NR, T> ml = rows_dot_mem<WT, NR, T>(W, ld, lane, ncs & ~(kLdAlign - 1), ld, [=](int m, int j) {
             return rd_x(xa + (size_t)min(e0 + m, elast) * xs, j, ncs);
         });
+        const int o0 = g * NR, o = o0 + lane;
+        if constexpr (kMode == kReadML) {  // every lane holds all the sums after the butterfly; lane 0 writes them
+            if (lane == 0) {
+#pragma unroll
+                for (int m = 0; m < T; ++m) {
+                    if (m < tm) {
+                        double *p = part + (size_t)(e0 + m) * mem.ps + (size_t)r * nout_pad + o0;
+#pragma unroll
+                        for (int q = 0; q < NR; ++q) p[q] = ml.v[m][q];
+                    }
+                }
+            }
+            continue;
+        }
         // lane q finishes row o0 + q of each member with v_p (vp_sum) + v_ml, as k_res_readout does
         // (each member's sum picked before the first v_p, so the T * NR sums are dead by then)
-        const int o0 = g * NR, o = o0 + lane;
         double vmls[T];
 #pragma unroll
         for (int m = 0; m < T; ++m) {
@@ -206,6 +232,137 @@ __global__ __launch_bounds__(512) void k_res_readout_mem(const RegionDev *__rest
                         unstd(vp + vml, meanstd + (size_t)r * 2 * kMeanStd, outl[o]);
                 }
             }
+        }
+    }
+}
+
+// k_res_finish with a member dimension (sml_res_step_finish_members): one thread per
+// (member, region, output): vp_sum on member e's local model, plus member e's partial sum,
+// then unstd -- k_res_finish's expression on one member's data
+template <typename WT>
+__global__ __launch_bounds__(256) void k_res_finish_mem(const RegionDev *__restrict__ R, const WT *__restrict__ wlm,
+                                                        const double *__restrict__ local_model,
+                                                        const double *__restrict__ meanstd,
+                                                        const int8_t *__restrict__ outl,
+                                                        const double *__restrict__ part, double *__restrict__ outvec,
+                                                        int nout, int ov_ld, int nout_pad, int ncs, int nlocal,
+                                                        MemberArgs mem) {
+    const int per = nlocal * nout_pad;
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= (int64_t)per * mem.members) return;
+    const int e = (int)(t / per), tr = (int)(t % per);
+    const int r = tr / nout_pad, o = tr % nout_pad;
+    if (o >= nout) return;
+    const double vp = vp_sum(wlm + R[r].wlm, nout_pad, local_model + (size_t)e * mem.lms + (size_t)r * ncs, ncs, o);
+    const double v = vp + part[(size_t)e * mem.ps + (size_t)r * nout_pad + o];
+    outvec[(size_t)e * mem.ovs + (size_t)r * ov_ld + o] = unstd(v, meanstd + (size_t)r * 2 * kMeanStd, outl[o]);
+}
+
+// where the members' forecast grids, local models, outvecs, partial sums and assembled
+// grids are: member e at e * stride doubles of each
+struct FinMemArgs {
+    int members, tile, tiles;
+    int64_t fc4s, fc2s, lms, ovs, ps, g4s, g2s;
+};
+
+// k_res_finish_grid for a tile of members (sml_res_step_finish_grid_members /
+// _assemble_members): one block per (region, tile of TF members at most).  The block loads
+// its W_out(:, 1:ncs) quads and the gather's tables, mean and std once, issues the gathers of
+// all the tile's members together into slm[m] (their round trips overlap), and after one
+// barrier forms each member's grouped sums in red[m] from the same quads -- per member the
+// chain k_res_finish_grid runs over the same columns, the groups added in group order --
+// then, after a second barrier, each member's outputs: unstd(vp + part) into that member's
+// outvec and, with kAsm, assemble_one into that member's grids.  Ungrouped: vp_sum over
+// slm[m].  Nothing is summed across members.  No in-kernel forecast wait: that is the
+// hybrid loop's.
+template <typename WT, bool kAsm, bool kGrouped, int TF>
+__global__ __launch_bounds__(256) void k_res_finish_grid_mem(
+    const RegionDev *__restrict__ R, const WT *__restrict__ wlm, const int32_t *__restrict__ src,
+    const uint8_t *__restrict__ lidx, const double *__restrict__ fc4, const double *__restrict__ fc2,
+    double *__restrict__ lm_out, const double *__restrict__ meanstd, const int8_t *__restrict__ outl,
+    const double *__restrict__ part, double *__restrict__ outvec, int nout, int ov_ld, int nout_pad, int ncs,
+    const int32_t *__restrict__ asm_dst, double *__restrict__ g4, double *__restrict__ g2, double *__restrict__ pr,
+    FinMemArgs mem) {
+    static_assert(TF >= 1 && TF <= kFinTileMax, "the tile's bound");
+    __shared__ double slm[TF][kMaxNcs];
+    __shared__ double red[kGrouped ? TF * kFinGroups * kFinOutMax : 1];
+    const int r = blockIdx.x / mem.tiles, e0 = (blockIdx.x % mem.tiles) * mem.tile;
+    const int tm = min(min(mem.tile, TF), mem.members - e0);  // >= 1: tiles = ceil(members / tile)
+    const int t = threadIdx.x;
+    const double *ms = meanstd + (size_t)r * 2 * kMeanStd;
+    const WT *wl = wlm + R[r].wlm;
+    const int nq = nout_pad / 4, gsz = fin_gsz(ncs);
+    const int q = t % nq, g = t / nq;
+    const int j0 = g * gsz, j1 = min(ncs, j0 + gsz);
+    Quad<WT> w[kFinGsz];
+    if constexpr (kGrouped) {  // (k_res_finish_grid's loads: every one issued, unpredicated)
+        const int gq = g < kFinGroups ? g : 0;
+        const int jlast = max(ncs - 1, 0);
+#pragma unroll
+        for (int jj = 0; jj < kFinGsz; ++jj)
+            w[jj] = load_quad(wl + (size_t)min(gq * gsz + jj, jlast) * nout_pad + 4 * q);
+    }
+    const bool gj = t < ncs;  // ncs <= kMaxNcs = blockDim: one entry per thread
+    SML_TL_SCOPE(sml::tl::kFinish);
+    if (gj) {
+        const int en = r * ncs + t;
+        const int gs = src[en];
+        const int l = lidx[en];
+        const double gmean = ms[l], gstd = ms[kMeanStd + l];
+        double v[TF];
+#pragma unroll
+        for (int m = 0; m < TF; ++m) {  // the tile's gathers, all in flight
+            const size_t e = (size_t)(e0 + min(m, tm - 1));
+            v[m] = gs < kGrid4d ? fc4[e * mem.fc4s + gs] : fc2[e * mem.fc2s + (gs - kGrid4d)];
+        }
+#pragma unroll
+        for (int m = 0; m < TF; ++m) {
+            if (m < tm) {
+                const double d = v[m] - gmean;
+                const double x = d / gstd;
+                slm[m][t] = x;
+                if (lm_out) lm_out[(size_t)(e0 + m) * mem.lms + (size_t)r * ncs + t] = x;
+            }
+        }
+    }
+    __syncthreads();
+    if constexpr (kGrouped) {
+        __builtin_amdgcn_sched_barrier(0);  // (the quads stay in their storage precision until here)
+        if (g < kFinGroups) {
+#pragma unroll 1
+            for (int m = 0; m < tm; ++m) {
+                double acc[4] = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+                for (int jj = 0; jj < kFinGsz; ++jj)
+                    if (j0 + jj < j1) {
+                        const double x = slm[m][j0 + jj];
+#pragma unroll
+                        for (int k = 0; k < 4; ++k) acc[k] = fma((double)w[jj].v[k], x, acc[k]);
+                    }
+                double *rm = red + (size_t)m * kFinGroups * kFinOutMax;
+#pragma unroll
+                for (int k = 0; k < 4; ++k) rm[g * nout_pad + 4 * q + k] = acc[k];
+            }
+        }
+        __syncthreads();
+    }
+    for (int o = t; o < nout; o += blockDim.x) {
+        const int l = outl[o];
+        const int d = kAsm ? asm_dst[(size_t)r * nout + o] : -1;
+        for (int m = 0; m < tm; ++m) {
+            const size_t e = (size_t)(e0 + m);
+            double vp;
+            if constexpr (kGrouped) {
+                const double *rm = red + (size_t)m * kFinGroups * kFinOutMax;
+                vp = rm[o];
+#pragma unroll
+                for (int gg = 1; gg < kFinGroups; ++gg) vp = vp + rm[gg * nout_pad + o];
+            } else {
+                vp = vp_sum(wl, nout_pad, slm[m], ncs, o);
+            }
+            const double v = unstd(vp + part[e * mem.ps + (size_t)r * nout_pad + o], ms, l);
+            outvec[e * mem.ovs + (size_t)r * ov_ld + o] = v;
+            if constexpr (kAsm) assemble_one(d, v, g4 + e * mem.g4s, g2 + e * mem.g2s, pr + e * mem.g2s);
         }
     }
 }

@@ -107,7 +107,9 @@ struct sml_reservoirs : PoolPlan {
     void *d_zero = nullptr;       // 256 zero bytes: the target of the balanced update's unused loads
     double *d_x[2] = {nullptr, nullptr};
     double *d_meanstd = nullptr;
-    double *d_part = nullptr;       // [nlocal][nout_pad] W_out(:, ncs+1:) x~ of the step in flight
+    // [members][nlocal][nout_pad] W_out(:, ncs+1:) x~ of the step in flight (member e's sums at
+    // e * nlocal * nout_pad: sml_res_set_members lays it out with the states)
+    double *d_part = nullptr;
     // cap on the waves of the v_ml readout (the half that runs beside SPEEDY's window;
     // 0: one wave per item).  Sharing CUs with SPEEDY, uncapped it takes ~6 TB/s and
     // SPEEDY's latency-bound kernels stall behind it; paced at 2048 waves (~4.7 TB/s)
@@ -139,6 +141,8 @@ struct sml_reservoirs : PoolPlan {
     // kernels' tiles (member_shape), kept with the step's shape
     int members = 1;
     MemberShape mshape;
+    MemberFinish mfin;      // the members' grid finish: its tile (member_finish)
+    int fin_tile_want = 0;  // 0: the build's tile; else a measurement's choice (sml_res_dbg_set_finish_tile)
     int32_t *d_tgt_idx = nullptr;  // [nlocal][nout] the targets' positions in each region's feedback
     // the next grid finish waits in-kernel for *fin_wflag >= fin_wval (sml::res_finish_wait)
     const uint64_t *fin_wflag = nullptr;
@@ -258,6 +262,7 @@ void reshape(sml_reservoirs *c) {
     c->shape = step_shape({c->maxn, c->maxninp, c->nout_pad, c->ncs, c->nlocal, c->max_lds, ell_ok, c->begin_mode,
                            c->per_region, c->finish_ungrouped, c->stepwise_drive});
     c->mshape = member_shape({c->members, c->shape.lds_region, c->shape.region_lds, c->max_lds});
+    c->mfin = member_finish(c->members, c->fin_tile_want);
 }
 
 // the calls that advance one state through the single-member kernels: refused while the
@@ -611,15 +616,18 @@ void launch_readout(sml_reservoirs *c, const double *xs, const double *d_local_m
 }
 
 // the finish from SPEEDY's forecast grids (k_res_finish_grid), grouped where the shape
-// allows, with or without the assembly
+// allows, with or without the assembly.  part: the partial sums it adds (c->d_part, or one
+// member's rows of it)
 template <bool kAsm>
 void launch_finish_grid(sml_reservoirs *c, const double *d_fc4d, const double *d_fc2d, double *d_local_model,
-                        double *d_outvec, double *d_grid4d, double *d_grid2d, double *d_precip, hipStream_t st) {
+                        double *d_outvec, double *d_grid4d, double *d_grid2d, double *d_precip, hipStream_t st,
+                        const double *part = nullptr) {
+    if (!part) part = c->d_part;
     with_wt(c, [&](auto tag) {
         using WT = decltype(tag);
         auto go = [&](auto kern) {
             hipLaunchKernelGGL(kern, dim3(c->nlocal), dim3(256), 0, st, c->d_rd, (const WT *)c->d_wlm, c->d_lm_src,
-                               c->d_lm_l, d_fc4d, d_fc2d, d_local_model, c->d_meanstd, c->d_outl, c->d_part, d_outvec,
+                               c->d_lm_l, d_fc4d, d_fc2d, d_local_model, c->d_meanstd, c->d_outl, part, d_outvec,
                                c->nout, c->ov_ld, c->nout_pad, c->ncs, c->d_asm_dst, d_grid4d, d_grid2d, d_precip,
                                c->fin_wflag, c->fin_wval, c->fin_wlate, c->fin_wtimeout);
         };
@@ -660,25 +668,81 @@ int launch_update_mem(sml_reservoirs *c, const double *xo, double *xn, const dou
     return SML_OK;
 }
 
-// xs: the state buffer the update just wrote (member e's x_aug rows at e * tot_xaug)
+// the partial sums of one member of a begun step
+int64_t part_stride(const sml_reservoirs *c) { return (int64_t)c->nlocal * c->nout_pad; }
+
+// xs: the state buffer the update just wrote (member e's x_aug rows at e * tot_xaug).
+// kReadML (the members' begin): v_ml alone into c->d_part; c->read_waves > 0 caps the
+// launch's waves, as it paces k_res_readout<kReadML> (the kernel strides over its items)
+template <int kMode>
 int launch_readout_mem(sml_reservoirs *c, const double *xs, const double *d_local_model, int64_t lm_stride,
                        double *d_outvec, int64_t ov_stride, hipStream_t st) {
     const StepShape &s = c->shape;
     const MemberShape &ms = c->mshape;
-    const int nitems = c->nlocal * s.groups, nwaves = nitems * ms.readout_streams;
+    const int nitems = c->nlocal * s.groups;
+    int nwaves = nitems * ms.readout_streams;
+    if (kMode == kReadML && c->read_waves > 0) nwaves = std::min(nwaves, c->read_waves);
     const int nblocks = (nwaves + s.wpb - 1) / s.wpb;
-    const MemberArgs mem{c->members, ms.readout_tile, c->tot_xaug, 0, lm_stride, ov_stride};
+    const MemberArgs mem{c->members, ms.readout_tile, c->tot_xaug, 0, lm_stride, ov_stride, part_stride(c)};
     with_wt(c, [&](auto tag) {
         using WT = decltype(tag);
         auto go = [&](auto kern) {
             hipLaunchKernelGGL(kern, dim3(nblocks), dim3(64 * s.wpb), 0, st, c->d_rd, (const WT *)c->d_wout,
-                               (const WT *)c->d_wlm, xs, d_local_model, c->d_meanstd, c->d_outl, d_outvec, c->nout,
-                               c->ov_ld, c->nout_pad, c->ncs, s.groups, nitems, ms.readout_streams, mem);
+                               (const WT *)c->d_wlm, xs, d_local_model, c->d_meanstd, c->d_outl, c->d_part, d_outvec,
+                               c->nout, c->ov_ld, c->nout_pad, c->ncs, s.groups, nitems, ms.readout_streams, mem);
         };
         if (kMemberTile == 2 || ms.readout_tile <= 2)
-            s.wide ? go(k_res_readout_mem<WT, kReadFull, kRowsWide, 2>) : go(k_res_readout_mem<WT, kReadFull, kRows, 2>);
+            s.wide ? go(k_res_readout_mem<WT, kMode, kRowsWide, 2>) : go(k_res_readout_mem<WT, kMode, kRows, 2>);
         else if constexpr (kMemberTile > 2)
-            s.wide ? go(k_res_readout_mem<WT, kReadFull, kRowsWide, 4>) : go(k_res_readout_mem<WT, kReadFull, kRows, 4>);
+            s.wide ? go(k_res_readout_mem<WT, kMode, kRowsWide, 4>) : go(k_res_readout_mem<WT, kMode, kRows, 4>);
+    });
+    SML_HIP(hipGetLastError());
+    return SML_OK;
+}
+
+// the members' finish from local models (k_res_finish_mem)
+int launch_finish_mem(sml_reservoirs *c, const double *d_local_model, int64_t lm_stride, double *d_outvec,
+                      int64_t ov_stride, hipStream_t st) {
+    const int64_t total = (int64_t)c->members * c->nlocal * c->nout_pad;
+    const MemberArgs mem{c->members, 1, 0, 0, lm_stride, ov_stride, part_stride(c)};
+    with_wt(c, [&](auto tag) {
+        using WT = decltype(tag);
+        hipLaunchKernelGGL(k_res_finish_mem<WT>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, c->d_rd,
+                           (const WT *)c->d_wlm, d_local_model, c->d_meanstd, c->d_outl, c->d_part, d_outvec, c->nout,
+                           c->ov_ld, c->nout_pad, c->ncs, c->nlocal, mem);
+    });
+    SML_HIP(hipGetLastError());
+    return SML_OK;
+}
+
+// the members' finish from their forecast grids (k_res_finish_grid_mem), a block per
+// (region, tile of c->mfin.tile members); c->mfin.looped: k_res_finish_grid once per member
+// on that member's pointers instead (the same bits)
+template <bool kAsm>
+int launch_finish_grid_mem(sml_reservoirs *c, const double *d_fc4d, const double *d_fc2d, double *d_local_model,
+                           double *d_outvec, double *d_grid4d, double *d_grid2d, double *d_precip,
+                           const FinMemArgs &a, hipStream_t st) {
+    if (c->mfin.looped) {
+        for (int64_t e = 0; e < c->members; ++e)
+            launch_finish_grid<kAsm>(c, d_fc4d ? d_fc4d + e * a.fc4s : nullptr, d_fc2d ? d_fc2d + e * a.fc2s : nullptr,
+                                     d_local_model ? d_local_model + e * a.lms : nullptr, d_outvec + e * a.ovs,
+                                     kAsm ? d_grid4d + e * a.g4s : nullptr, kAsm ? d_grid2d + e * a.g2s : nullptr,
+                                     kAsm ? d_precip + e * a.g2s : nullptr, st, c->d_part + e * a.ps);
+        SML_HIP(hipGetLastError());
+        return SML_OK;
+    }
+    with_wt(c, [&](auto tag) {
+        using WT = decltype(tag);
+        auto go = [&](auto kern) {
+            hipLaunchKernelGGL(kern, dim3(c->nlocal * a.tiles), dim3(256), 0, st, c->d_rd, (const WT *)c->d_wlm,
+                               c->d_lm_src, c->d_lm_l, d_fc4d, d_fc2d, d_local_model, c->d_meanstd, c->d_outl,
+                               c->d_part, d_outvec, c->nout, c->ov_ld, c->nout_pad, c->ncs, c->d_asm_dst, d_grid4d,
+                               d_grid2d, d_precip, a);
+        };
+        const bool grp = c->shape.finish_grouped;
+        if (a.tile <= 2) grp ? go(k_res_finish_grid_mem<WT, kAsm, true, 2>) : go(k_res_finish_grid_mem<WT, kAsm, false, 2>);
+        else grp ? go(k_res_finish_grid_mem<WT, kAsm, true, kFinTileMax>)
+                 : go(k_res_finish_grid_mem<WT, kAsm, false, kFinTileMax>);
     });
     SML_HIP(hipGetLastError());
     return SML_OK;
@@ -831,12 +895,15 @@ extern "C" int sml_res_set_members(sml_reservoirs *c, int members) {
     double *nx[2] = {nullptr, nullptr};
     pool(c, &nx[0], (int64_t)members * c->tot_xaug, true);
     pool(c, &nx[1], (int64_t)members * c->tot_xaug, true);
+    double *npart = nullptr;  // scratch of the step in flight: nothing to keep
+    pool(c, &npart, (int64_t)members * std::max(c->nlocal, 1) * c->nout_pad);
     hipError_t e = hipSuccess;
     for (int q = 0; q < 2 && c->mem.status() == SML_OK && e == hipSuccess && keep > 0; ++q)
         e = hipMemcpy(nx[q], c->d_x[q], (size_t)keep * 8, hipMemcpyDeviceToDevice);
     if (c->mem.status() != SML_OK || e != hipSuccess) {
         c->mem.release(&nx[0]);
         c->mem.release(&nx[1]);
+        c->mem.release(&npart);
         return c->mem.status() ? c->mem.status()
                                : fail(SML_ERR_HIP, "sml_res_set_members: %s", hipGetErrorString(e));
     }
@@ -844,6 +911,8 @@ extern "C" int sml_res_set_members(sml_reservoirs *c, int members) {
         c->mem.release(&c->d_x[q]);
         c->d_x[q] = nx[q];
     }
+    c->mem.release(&c->d_part);
+    c->d_part = npart;
     c->members = members;
     reshape(c);
     return SML_OK;
@@ -976,14 +1045,9 @@ extern "C" int sml_res_kernel_times(sml_reservoirs *c, float *update_ms, float *
     return SML_OK;
 }
 
-extern "C" int sml_res_step_begin(sml_reservoirs *c, const double *d_feedback, void *stream) {
-    SML_REQUIRE(c, "null context");
-    if (int rc = check_single(c, "sml_res_step_begin")) return rc;
-    if (c->nlocal == 0) return SML_OK;
-    SML_REQUIRE(d_feedback, "null device buffer");
-    if (c->is_begun()) return fail(SML_ERR_STATE, "sml_res_step_begin called twice without sml_res_step_finish");
-    if (int rc = check_loaded(c)) return rc;
-    hipStream_t st = (hipStream_t)stream;
+namespace {
+// one member's begin (sml_res_step_begin; sml_res_step_begin_members at one member)
+int begin_single(sml_reservoirs *c, const double *d_feedback, hipStream_t st) {
     return c->advance(true, [&](const double *xo, double *xn) {
         StepTimer timer(c, st);
         if (int rc = timer.stamp(0)) return rc;
@@ -998,6 +1062,17 @@ extern "C" int sml_res_step_begin(sml_reservoirs *c, const double *d_feedback, v
         SML_HIP(hipGetLastError());
         return timer.stamp(2);
     });
+}
+}  // namespace
+
+extern "C" int sml_res_step_begin(sml_reservoirs *c, const double *d_feedback, void *stream) {
+    SML_REQUIRE(c, "null context");
+    if (int rc = check_single(c, "sml_res_step_begin")) return rc;
+    if (c->nlocal == 0) return SML_OK;
+    SML_REQUIRE(d_feedback, "null device buffer");
+    if (c->is_begun()) return fail(SML_ERR_STATE, "sml_res_step_begin called twice without sml_res_step_finish");
+    if (int rc = check_loaded(c)) return rc;
+    return begin_single(c, d_feedback, (hipStream_t)stream);
 }
 
 // discard a begun step (sml_res_step_begin without its finish): wait for it, then
@@ -1024,6 +1099,7 @@ extern "C" int sml_res_step_finish(sml_reservoirs *c, const double *d_local_mode
     SML_REQUIRE(d_outvec, "null device buffer");
     SML_REQUIRE(c->ncs == 0 || d_local_model, "hybrid context needs d_local_model");
     if (!c->is_begun()) return fail(SML_ERR_STATE, "sml_res_step_finish without sml_res_step_begin");
+    if (int rc = check_single(c, "sml_res_step_finish")) return rc;  // (it would finish member 0 alone and close the step)
     hipStream_t st = (hipStream_t)stream;
     launch_readout<kReadFinish>(c, nullptr, d_local_model, d_outvec, st);
     SML_HIP(hipGetLastError());
@@ -1071,6 +1147,7 @@ extern "C" int sml_res_step_finish_grid(sml_reservoirs *c, const double *d_fc4d,
     SML_REQUIRE(!c->generic || c->ncs == 0, "a generic (slab) context has no local-model tiling");
     SML_REQUIRE(c->ncs <= kMaxNcs, "ncs %d exceeds %d", c->ncs, kMaxNcs);
     if (!c->is_begun()) return fail(SML_ERR_STATE, "sml_res_step_finish_grid without sml_res_step_begin");
+    if (int rc = check_single(c, "sml_res_step_finish_grid")) return rc;  // (it would finish member 0 alone and close the step)
     launch_finish_grid<false>(c, d_fc4d, d_fc2d, d_local_model, d_outvec, nullptr, nullptr, nullptr,
                               (hipStream_t)stream);
     SML_HIP(hipGetLastError());
@@ -1095,6 +1172,7 @@ extern "C" int sml_res_step_finish_assemble(sml_reservoirs *c, const double *d_f
                 "null device buffer");
     SML_REQUIRE(c->ncs <= kMaxNcs, "ncs %d exceeds %d", c->ncs, kMaxNcs);
     if (!c->is_begun()) return fail(SML_ERR_STATE, "sml_res_step_finish_assemble without sml_res_step_begin");
+    if (int rc = check_single(c, "sml_res_step_finish_assemble")) return rc;  // (it would finish member 0 alone and close the step)
     launch_finish_grid<true>(c, d_fc4d, d_fc2d, d_local_model, d_outvec, d_grid4d, d_grid2d, d_precip,
                              (hipStream_t)stream);
     SML_HIP(hipGetLastError());
@@ -1178,7 +1256,7 @@ extern "C" int sml_res_step_members(sml_reservoirs *c, const double *d_feedback,
         } else {
             if (int rc = launch_update_mem(c, xo, xn, d_feedback, fb_stride, st)) return rc;
             if (int rc = timer.stamp(1)) return rc;
-            if (int rc = launch_readout_mem(c, xn, d_local_model, lm_stride, d_outvec, ov_stride, st)) return rc;
+            if (int rc = launch_readout_mem<kReadFull>(c, xn, d_local_model, lm_stride, d_outvec, ov_stride, st)) return rc;
         }
         return timer.stamp(2);
     });
@@ -1204,6 +1282,146 @@ extern "C" int sml_res_synchronize_members(sml_reservoirs *c, const double *d_in
             }))
             return rc;
     }
+    return SML_OK;
+}
+
+// ---- the split step for every member (sml_res_members.hpp): sml_res_step_begin_members
+// updates every member and leaves every member's v_ml in c->d_part; the three finishes add
+// each member's v_p.  At one member they are the single-member calls.
+namespace {
+int check_fb_stride(const sml_reservoirs *c, int64_t fb_stride) {
+    SML_REQUIRE(fb_stride >= c->tot_fb, "fb_stride %lld smaller than the packed feedback size %lld",
+                (long long)fb_stride, (long long)c->tot_fb);
+    return SML_OK;
+}
+int check_lm_ov_strides(const sml_reservoirs *c, int64_t lm_stride, int64_t ov_stride) {
+    SML_REQUIRE(c->ncs == 0 || lm_stride >= (int64_t)c->nlocal * c->ncs,
+                "lm_stride %lld smaller than nlocal * chunk_speedy", (long long)lm_stride);
+    SML_REQUIRE(ov_stride >= (int64_t)c->nlocal * c->ov_ld, "ov_stride %lld smaller than nlocal * the outvec row stride",
+                (long long)ov_stride);
+    return SML_OK;
+}
+
+// the grid finishes' common part; on success the step is closed
+template <bool kAsm>
+int finish_grid_members(sml_reservoirs *c, const char *what, const double *d_fc4d, int64_t fc4_stride,
+                        const double *d_fc2d, int64_t fc2_stride, double *d_local_model, int64_t lm_stride,
+                        double *d_outvec, int64_t ov_stride, double *d_grid4d, int64_t g4_stride, double *d_grid2d,
+                        double *d_precip, int64_t g2_stride, void *stream) {
+    SML_REQUIRE(c, "null context");
+    if (kAsm)
+        SML_REQUIRE(sml::res_in_global_order(c), "the fused assembly needs every region on this rank, in global order");
+    if (c->nlocal == 0) return SML_OK;
+    SML_REQUIRE(d_outvec && (c->ncs == 0 || (d_fc4d && d_fc2d)), "null device buffer");
+    SML_REQUIRE(!kAsm || (d_grid4d && d_grid2d && d_precip), "null device buffer");
+    SML_REQUIRE(!c->generic || c->ncs == 0, "a generic (slab) context has no local-model tiling");
+    SML_REQUIRE(c->ncs <= kMaxNcs, "ncs %d exceeds %d", c->ncs, kMaxNcs);
+    SML_REQUIRE(c->ncs == 0 || fc4_stride >= kGrid4d, "fc4_stride %lld smaller than the 4-d grid's %d doubles",
+                (long long)fc4_stride, kGrid4d);
+    SML_REQUIRE(c->ncs == 0 || fc2_stride >= kGrid2d, "fc2_stride %lld smaller than the 2-d grid's %d doubles",
+                (long long)fc2_stride, kGrid2d);
+    if (int rc = check_lm_ov_strides(c, d_local_model ? lm_stride : (int64_t)c->nlocal * c->ncs, ov_stride)) return rc;
+    if (kAsm) {
+        SML_REQUIRE(g4_stride >= kGrid4d, "g4_stride %lld smaller than the 4-d grid's %d doubles", (long long)g4_stride,
+                    kGrid4d);
+        SML_REQUIRE(g2_stride >= kGrid2d, "g2_stride %lld smaller than the 2-d grid's %d doubles", (long long)g2_stride,
+                    kGrid2d);
+    }
+    if (!c->is_begun()) return fail(SML_ERR_STATE, "%s without sml_res_step_begin_members", what);
+    hipStream_t st = (hipStream_t)stream;
+    if (c->members == 1) {  // the single-member kernel itself
+        launch_finish_grid<kAsm>(c, d_fc4d, d_fc2d, d_local_model, d_outvec, d_grid4d, d_grid2d, d_precip, st);
+        SML_HIP(hipGetLastError());
+    } else {
+        const FinMemArgs a{c->members, c->mfin.tile, c->mfin.tiles, fc4_stride, fc2_stride, lm_stride, ov_stride,
+                           part_stride(c), g4_stride, g2_stride};
+        if (int rc = launch_finish_grid_mem<kAsm>(c, d_fc4d, d_fc2d, d_local_model, d_outvec, d_grid4d, d_grid2d,
+                                                  d_precip, a, st))
+            return rc;
+    }
+    c->close();
+    return SML_OK;
+}
+}  // namespace
+
+extern "C" int sml_res_step_begin_members(sml_reservoirs *c, const double *d_feedback, int64_t fb_stride,
+                                          void *stream) {
+    SML_REQUIRE(c, "null context");
+    if (c->nlocal == 0) return SML_OK;
+    SML_REQUIRE(d_feedback, "null device buffer");
+    if (int rc = check_fb_stride(c, fb_stride)) return rc;
+    if (c->is_begun())
+        return fail(SML_ERR_STATE, "sml_res_step_begin_members called twice without a members finish");
+    if (int rc = check_loaded(c)) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    if (c->members == 1) return begin_single(c, d_feedback, st);  // sml_res_step_begin's kernels, the fused begin too
+    // two launches; one swap covers all members (and one roll-back: sml_res_step_cancel)
+    return c->advance(true, [&](const double *xo, double *xn) {
+        StepTimer timer(c, st);
+        if (int rc = timer.stamp(0)) return rc;
+        if (int rc = launch_update_mem(c, xo, xn, d_feedback, fb_stride, st)) return rc;
+        if (int rc = timer.stamp(1)) return rc;
+        if (int rc = launch_readout_mem<kReadML>(c, xn, nullptr, 0, nullptr, 0, st)) return rc;
+        return timer.stamp(2);
+    });
+}
+
+extern "C" int sml_res_step_finish_members(sml_reservoirs *c, const double *d_local_model, int64_t lm_stride,
+                                           double *d_outvec, int64_t ov_stride, void *stream) {
+    SML_REQUIRE(c, "null context");
+    if (c->nlocal == 0) return SML_OK;
+    SML_REQUIRE(d_outvec, "null device buffer");
+    SML_REQUIRE(c->ncs == 0 || d_local_model, "hybrid context needs d_local_model");
+    if (int rc = check_lm_ov_strides(c, lm_stride, ov_stride)) return rc;
+    if (!c->is_begun()) return fail(SML_ERR_STATE, "sml_res_step_finish_members without sml_res_step_begin_members");
+    hipStream_t st = (hipStream_t)stream;
+    if (c->ncs == 0) {
+        d_local_model = nullptr;
+        lm_stride = 0;
+    }
+    if (c->members == 1) {
+        launch_readout<kReadFinish>(c, nullptr, d_local_model, d_outvec, st);
+        SML_HIP(hipGetLastError());
+    } else if (int rc = launch_finish_mem(c, d_local_model, lm_stride, d_outvec, ov_stride, st)) {
+        return rc;
+    }
+    c->close();
+    return SML_OK;
+}
+
+extern "C" int sml_res_step_finish_grid_members(sml_reservoirs *c, const double *d_fc4d, int64_t fc4_stride,
+                                                const double *d_fc2d, int64_t fc2_stride, double *d_local_model,
+                                                int64_t lm_stride, double *d_outvec, int64_t ov_stride,
+                                                void *stream) {
+    return finish_grid_members<false>(c, "sml_res_step_finish_grid_members", d_fc4d, fc4_stride, d_fc2d, fc2_stride,
+                                      d_local_model, lm_stride, d_outvec, ov_stride, nullptr, 0, nullptr, nullptr, 0,
+                                      stream);
+}
+
+extern "C" int sml_res_step_finish_assemble_members(sml_reservoirs *c, const double *d_fc4d, int64_t fc4_stride,
+                                                    const double *d_fc2d, int64_t fc2_stride, double *d_local_model,
+                                                    int64_t lm_stride, double *d_outvec, int64_t ov_stride,
+                                                    double *d_grid4d, int64_t g4_stride, double *d_grid2d,
+                                                    double *d_precip, int64_t g2_stride, void *stream) {
+    return finish_grid_members<true>(c, "sml_res_step_finish_assemble_members", d_fc4d, fc4_stride, d_fc2d,
+                                     fc2_stride, d_local_model, lm_stride, d_outvec, ov_stride, d_grid4d, g4_stride,
+                                     d_grid2d, d_precip, g2_stride, stream);
+}
+
+// the members one block of the grid finish serves (member_finish; 1 at members > 1: the
+// single-member kernel once per member)
+extern "C" int sml_res_member_finish_tile(const sml_reservoirs *c, int *finish_tile) {
+    SML_REQUIRE(c && finish_tile, "null argument");
+    *finish_tile = c->mfin.tile;
+    return SML_OK;
+}
+
+// a measurement's choice of that tile (tools/probe_members_split.py; not in the public
+// header): 0 the build's, 1 the looped single-member kernel, 2 .. kFinTileMax
+extern "C" int sml_res_dbg_set_finish_tile(sml_reservoirs *c, int tile) {
+    SML_REQUIRE(c && tile >= 0 && tile <= kFinTileMax, "bad argument");
+    c->fin_tile_want = tile;
+    reshape(c);
     return SML_OK;
 }
 

@@ -108,6 +108,17 @@ MemberShape member_shape(const MemberShapeIn &in) {
     return m;
 }
 
+MemberFinish member_finish(int members, int want) {
+    MemberFinish f;
+    const int cap = want >= 1 && want <= kFinTileMax ? want : kFinTile;
+    f.tile = std::max(1, std::min(members, cap));
+    f.tiles = (std::max(members, 1) + f.tile - 1) / f.tile;
+    f.looped = f.tile == 1 && members > 1;
+    // slm[tile][kMaxNcs] and red[tile][kFinGroups][kFinOutMax] doubles
+    f.lds = (size_t)f.tile * (kMaxNcs + (size_t)kFinGroups * kFinOutMax) * sizeof(double);
+    return f;
+}
+
 template <typename SrcT, typename StoT>
 int pack_region(const PackIn &in, const RegionDev &rg, const int *rows, const int *cols, const SrcT *vals,
                 const SrcT *win, const SrcT *wout, PackedRegion<StoT> *out) {

@@ -146,6 +146,27 @@ struct MemberShape {
 
 MemberShape member_shape(const MemberShapeIn &in);
 
+// The members' finish from forecast grids (k_res_finish_grid_mem): one block per (region,
+// tile of members), the tile's gathers in flight together, about 10 KB of LDS a member.
+// kFinTileMax: the compile-time bound of the tile; kFinTile: the tile of the build.  A tile
+// of 1 is the single-member kernel once per member on the members' pointers: the same bits.
+constexpr int kFinTileMax = 4;
+#ifndef SML_MEMBER_FIN_TILE
+#define SML_MEMBER_FIN_TILE 4  // profiles/members.md
+#endif
+constexpr int kFinTile = SML_MEMBER_FIN_TILE;
+static_assert(kFinTile >= 1 && kFinTile <= kFinTileMax, "the members finish is built for tiles of 1 .. kFinTileMax");
+
+struct MemberFinish {
+    int tile;     // members a block of k_res_finish_grid_mem serves (TF)
+    int tiles;    // blocks per region: ceil(members / tile)
+    bool looped;  // tile 1 at members > 1: k_res_finish_grid once per member instead
+    size_t lds;   // the block's LDS at that tile, in bytes
+};
+
+// want: 0 the build's tile, 1 .. kFinTileMax that tile (a measurement's choice)
+MemberFinish member_finish(int members, int want = 0);
+
 // ------------------------------------------------------------------ one region's weights
 // what sml_res_load_region uploads, in the storage dtype: A and W_in as CSR, W_out
 // transposed and padded (wt [nout_pad][ld]) with its local-model block (wl [ncs][nout_pad]),

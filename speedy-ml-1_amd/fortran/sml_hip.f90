@@ -211,6 +211,43 @@ module sml_hip
       integer(c_int), intent(out) :: update_tile, update_lds, readout_tile
       integer(c_int) :: rc
     end function
+    ! the split step for every member (begin: update + v_ml; the finishes: v_p per member from its
+    ! local model, or tiled from its forecast grids, with or without the assembly into its grids)
+    function sml_res_step_begin_members(ctx, d_feedback, fb_stride, stream) &
+        bind(C, name='sml_res_step_begin_members') result(rc)
+      import :: c_ptr, c_int, c_int64_t
+      type(c_ptr), value :: ctx, d_feedback, stream
+      integer(c_int64_t), value :: fb_stride
+      integer(c_int) :: rc
+    end function
+    function sml_res_step_finish_members(ctx, d_local_model, lm_stride, d_outvec, ov_stride, stream) &
+        bind(C, name='sml_res_step_finish_members') result(rc)
+      import :: c_ptr, c_int, c_int64_t
+      type(c_ptr), value :: ctx, d_local_model, d_outvec, stream
+      integer(c_int64_t), value :: lm_stride, ov_stride
+      integer(c_int) :: rc
+    end function
+    function sml_res_step_finish_grid_members(ctx, d_fc4d, fc4_stride, d_fc2d, fc2_stride, d_local_model, &
+        lm_stride, d_outvec, ov_stride, stream) bind(C, name='sml_res_step_finish_grid_members') result(rc)
+      import :: c_ptr, c_int, c_int64_t
+      type(c_ptr), value :: ctx, d_fc4d, d_fc2d, d_local_model, d_outvec, stream
+      integer(c_int64_t), value :: fc4_stride, fc2_stride, lm_stride, ov_stride
+      integer(c_int) :: rc
+    end function
+    function sml_res_step_finish_assemble_members(ctx, d_fc4d, fc4_stride, d_fc2d, fc2_stride, d_local_model, &
+        lm_stride, d_outvec, ov_stride, d_grid4d, g4_stride, d_grid2d, d_precip, g2_stride, stream) &
+        bind(C, name='sml_res_step_finish_assemble_members') result(rc)
+      import :: c_ptr, c_int, c_int64_t
+      type(c_ptr), value :: ctx, d_fc4d, d_fc2d, d_local_model, d_outvec, d_grid4d, d_grid2d, d_precip, stream
+      integer(c_int64_t), value :: fc4_stride, fc2_stride, lm_stride, ov_stride, g4_stride, g2_stride
+      integer(c_int) :: rc
+    end function
+    function sml_res_member_finish_tile(ctx, finish_tile) bind(C, name='sml_res_member_finish_tile') result(rc)
+      import :: c_ptr, c_int
+      type(c_ptr), value :: ctx
+      integer(c_int), intent(out) :: finish_tile
+      integer(c_int) :: rc
+    end function
 
     ! predict split at column chunk_size_speedy (v_ml + v_p, mod_reservoir.f90:1456-1459)
     function sml_res_step_begin(ctx, d_feedback, stream) bind(C, name='sml_res_step_begin') result(rc)

@@ -67,6 +67,8 @@ EXPORTED = (
     "sml_res_spectral_radius", "sml_gen_region",
     "sml_res_set_members", "sml_res_members", "sml_res_set_state_member", "sml_res_get_state_member",
     "sml_res_step_members", "sml_res_synchronize_members", "sml_res_member_tile",
+    "sml_res_step_begin_members", "sml_res_step_finish_members", "sml_res_step_finish_grid_members",
+    "sml_res_step_finish_assemble_members", "sml_res_member_finish_tile",
 )
 
 SML_HOP_AUTO, SML_HOP_WAIT_VALUE, SML_HOP_EVENTS, SML_HOP_KERNEL = 0, 1, 2, 3
@@ -112,6 +114,7 @@ def _declare(L: ctypes.CDLL) -> None:
     vp, i, d, i64p = ctypes.c_void_p, ctypes.c_int, ctypes.c_double, ctypes.POINTER(ctypes.c_int64)
     pp = ctypes.POINTER(ctypes.c_void_p)
     ip = ctypes.POINTER(ctypes.c_int)
+    i64 = ctypes.c_int64
     L.sml_last_error.restype = ctypes.c_char_p
     L.sml_last_error.argtypes = []
     L.sml_abi_version.restype = i
@@ -282,6 +285,11 @@ def _declare(L: ctypes.CDLL) -> None:
         "sml_res_step_members": [vp, vp, ctypes.c_int64, vp, ctypes.c_int64, vp, ctypes.c_int64, vp],
         "sml_res_synchronize_members": [vp, vp, i, ctypes.c_int64, ctypes.c_int64, vp],
         "sml_res_member_tile": [vp, ip, ip, ip],
+        "sml_res_step_begin_members": [vp, vp, i64, vp],
+        "sml_res_step_finish_members": [vp, vp, i64, vp, i64, vp],
+        "sml_res_step_finish_grid_members": [vp, vp, i64, vp, i64, vp, i64, vp, i64, vp],
+        "sml_res_step_finish_assemble_members": [vp, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, vp, i64, vp],
+        "sml_res_member_finish_tile": [vp, ip],
     }
     for name, args in sig.items():
         if os.environ.get("SML_LIB") and not hasattr(L, name):

@@ -169,6 +169,94 @@ class Reservoirs:
         check(lib().sml_res_step_members(self._h, ptr(d_feedback), fbs, ptr(d_local_model if self.ncs else None), lms,
                                          ptr(d_outvec), ovs, stream_ptr(stream)))
 
+    # --- the split step for every member (sml_res_step_begin_members and its finishes)
+    def _member_lm_ov(self, d_local_model, d_outvec, lm_optional=False):
+        """The strides of d_local_model [E, nlocal, chunk_speedy] (None allowed when
+        chunk_speedy == 0, or where the call only writes it) and d_outvec [E, nlocal, ld]."""
+        E = self.members
+        lms = self.nlocal * self.ncs
+        if d_local_model is None or not self.ncs:
+            if self.ncs and not lm_optional:
+                raise ValueError("d_local_model: a hybrid context needs it")
+        else:
+            lms = self._member_rows(d_local_model, "d_local_model", (E, self.nlocal), self.ncs)
+            if d_local_model.shape[-1] != self.ncs:
+                raise ValueError(f"d_local_model: rows of {self.ncs} doubles expected")
+        ovs = self._member_rows(d_outvec, "d_outvec", (E, self.nlocal), self._ov_ld)
+        if d_outvec.shape[-1] != self._ov_ld:
+            raise ValueError(f"d_outvec: rows of {self._ov_ld} doubles expected (set_outvec_ld)")
+        return lms, ovs
+
+    def _member_grids(self, g4, g2, names, pr=None):
+        """The strides of a members' 4-d grid [E, 8, 48, 96, 4] and 2-d grid(s) [E, 48, 96]
+        (pr, when given, with g2's stride)."""
+        E = self.members
+        s4 = self._member_rows(g4, names[0], (E, 8, 48, 96), 4)
+        if g4.shape[-1] != 4:
+            raise ValueError(f"{names[0]}: shape ({E}, 8, 48, 96, 4) expected, got {tuple(g4.shape)}")
+        s2 = self._member_rows(g2, names[1], (E, 48), 96)
+        if g2.shape[-1] != 96:
+            raise ValueError(f"{names[1]}: shape ({E}, 48, 96) expected, got {tuple(g2.shape)}")
+        if pr is not None:
+            sp = self._member_rows(pr, names[2], (E, 48), 96)
+            if pr.shape[-1] != 96 or sp != s2:
+                raise ValueError(f"{names[2]}: shape ({E}, 48, 96) and {names[1]}'s member stride {s2} expected, "
+                                 f"got {tuple(pr.shape)} with stride {sp}")
+        return s4, s2
+
+    def begin_members(self, d_feedback, stream=None):
+        """predict_begin for every member (sml_res_step_begin_members): d_feedback
+        [E, >= total feedback]; every member's update and v_ml, no local model needed."""
+        fbs = self._member_rows(d_feedback, "d_feedback", (self.members,), int(self.fb_offsets[-1]))
+        check(lib().sml_res_step_begin_members(self._h, ptr(d_feedback), fbs, stream_ptr(stream)))
+
+    def finish_members(self, d_local_model, d_outvec, stream=None):
+        """predict_finish for every member (sml_res_step_finish_members): d_local_model
+        [E, nlocal, chunk_speedy] (None when chunk_speedy == 0), d_outvec [E, nlocal, ld]."""
+        lms, ovs = self._member_lm_ov(d_local_model, d_outvec)
+        check(lib().sml_res_step_finish_members(self._h, ptr(d_local_model if self.ncs else None), lms,
+                                                ptr(d_outvec), ovs, stream_ptr(stream)))
+
+    def finish_grid_members(self, d_fc4d, d_fc2d, d_local_model, d_outvec, stream=None):
+        """predict_finish_grid for every member (sml_res_step_finish_grid_members): member
+        e's local model is tiled from its forecast d_fc4d[e] / d_fc2d[e] ([E, 8, 48, 96, 4] /
+        [E, 48, 96]); d_local_model (or None) also receives the tiled vectors."""
+        s4, s2 = self._member_grids(d_fc4d, d_fc2d, ("d_fc4d", "d_fc2d"))
+        lms, ovs = self._member_lm_ov(d_local_model, d_outvec, lm_optional=True)
+        check(lib().sml_res_step_finish_grid_members(self._h, ptr(d_fc4d), s4, ptr(d_fc2d), s2,
+                                                     ptr(d_local_model if self.ncs else None), lms, ptr(d_outvec),
+                                                     ovs, stream_ptr(stream)))
+
+    def finish_assemble_members(self, d_fc4d, d_fc2d, d_local_model, d_outvec, g4, g2, pr, stream=None):
+        """predict_finish_assemble for every member (sml_res_step_finish_assemble_members):
+        member e's outputs are also scattered into g4[e], g2[e], pr[e] (one rank holding
+        every region in order)."""
+        s4, s2 = self._member_grids(d_fc4d, d_fc2d, ("d_fc4d", "d_fc2d"))
+        g4s, g2s = self._member_grids(g4, g2, ("g4", "g2", "pr"), pr=pr)
+        lms, ovs = self._member_lm_ov(d_local_model, d_outvec, lm_optional=True)
+        check(lib().sml_res_step_finish_assemble_members(self._h, ptr(d_fc4d), s4, ptr(d_fc2d), s2,
+                                                         ptr(d_local_model if self.ncs else None), lms,
+                                                         ptr(d_outvec), ovs, ptr(g4), g4s, ptr(g2), ptr(pr), g2s,
+                                                         stream_ptr(stream)))
+
+    def member_finish_tile(self) -> int:
+        """Members one block of the grid finish serves (sml_res_member_finish_tile); 1 at
+        more than one member: the single-member kernel once per member."""
+        v = ctypes.c_int()
+        check(lib().sml_res_member_finish_tile(self._h, ctypes.byref(v)))
+        return v.value
+
+    def cancel_step(self):
+        """Discard a begun step, of one member or of all (sml_res_step_cancel): the states
+        are what they were before the begin.  Waits for the device."""
+        check(lib().sml_res_step_cancel(self._h))
+
+    def step_begun(self) -> bool:
+        """Whether a begin's finish is pending (sml_res_step_begun)."""
+        v = ctypes.c_int()
+        check(lib().sml_res_step_begun(self._h, ctypes.byref(v)))
+        return bool(v.value)
+
     def synchronize_members(self, d_inputs, length: int, stream=None):
         """synchronize for every member (sml_res_synchronize_members): d_inputs
         [>= length, E, >= total feedback]; `length` updates of every member, no readout."""
