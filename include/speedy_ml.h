@@ -758,6 +758,17 @@ int sml_hybrid_get_feb29(const sml_hybrid *h, int *feb29);
 /* the tisr entries of every local region's feedback from one hour's global tisr
  * field d_tisr_grid(96, 48): overlap tile, (x - mean(34)) / std(34) */
 int sml_res_tile_tisr_field(sml_reservoirs *c, const double *d_tisr_grid, double *d_feedback, void *stream);
+/* sml_res_tile_feedback / sml_res_tile_tisr_field for every member of the context
+ * (sml_res_set_members), one launch each: member e's grids, precipitation and feedback
+ * start e * g4_stride / g2_stride (d_grid2d and d_precip) / fb_stride doubles into their
+ * arrays (each stride >= the packed size); d_tisr [nlocal][16] (or NULL: the tisr entries
+ * stay) and d_tisr_grid(96, 48) are the members' common ones.  Per member bitwise the
+ * single-member call; the feedback's sst entries are not written. */
+int sml_res_tile_feedback_members(sml_reservoirs *c, const double *d_grid4d, int64_t g4_stride,
+                                  const double *d_grid2d, const double *d_precip, int64_t g2_stride,
+                                  const double *d_tisr, double *d_feedback, int64_t fb_stride, void *stream);
+int sml_res_tile_tisr_field_members(sml_reservoirs *c, const double *d_tisr_grid, double *d_feedback,
+                                    int64_t fb_stride, void *stream);
 /* the loop's main (reservoir + exchange) and side (SPEEDY) streams */
 int sml_hybrid_streams(const sml_hybrid *h, void **main, void **side);
 /* the CU split of the two streams: SPEEDY's CUs [0, speedy_cus) and the reservoir's
@@ -810,6 +821,50 @@ int sml_hybrid_exchange_width(const sml_hybrid *h, int *width);
  * [timestep_slab/timestep - 1][*ring_len], the last slab feedback and slab outvecs */
 int sml_hybrid_slab_buffers(const sml_hybrid *h, const double **d_sst_grid, const double **d_ring, int *ring_len,
                             const double **d_slab_feedback, const double **d_slab_outvec);
+/* ---- the slab ocean of an E-member forecast on one rank (speedy_ml_amd.ensemble): the
+ * stages above with a member dimension, one launch per stage for all members, per member
+ * bitwise the single-member loop's.  atmo: the members' atmo context, every region in
+ * global order; slab: the slab context as sml_hybrid_set_slab describes it, with the same
+ * member count (sml_res_set_members on both first: E is the atmo context's).  Create
+ * applies sml_hybrid_set_slab's checks and sets the atmo context's outvec row stride to
+ * the exchange width (nout + resx*resy), so the members' outvecs are
+ * [E][nlocal][exchange width].  The caller owns those and the members' feedbacks and
+ * passes them with their member strides in doubles (>= the packed size); the slab
+ * feedbacks, slab outvecs, rings and sst grids are the object's (sml_slab_buffers).  The
+ * host calls, per step t + 1, in the single-member loop's order: sml_slab_predict(t + 1)
+ * before the atmo finish, sml_slab_sst after it (then sml_dyn_set_hybrid_sst of each
+ * member's grid when it wrote), and sml_slab_ring(t + 1) after the feedbacks' re-tiling. */
+typedef struct sml_slab sml_slab;
+int sml_slab_create(sml_reservoirs *atmo, sml_reservoirs *slab, const double *d_base_sst, const double *d_sea_mask,
+                    int timestep, int timestep_slab, double sst_bias, sml_slab **out);
+int sml_slab_destroy(sml_slab *s);
+/* members, doubles per exchange row, slab reservoirs, the ring's columns
+ * (timestep_slab/timestep - 1) and their length, current_sst_bias; any may be NULL */
+int sml_slab_info(const sml_slab *s, int *members, int *exchange_width, int *nslab, int *ring_columns,
+                  int *ring_len, double *sst_bias);
+/* start_prediction_slab's hand-over of one member: 272 K in the sst columns of its
+ * exchange rows, d_slab_outvec[nslab][resx*resy] (device, unstandardized) over them, its
+ * ring cleared, its SST marked changed.  The slabs' sst mean / std are taken at the first
+ * start.  d_outvec: the members' outvecs (member 0's).  Waits for `stream`. */
+int sml_slab_start(sml_slab *s, int member, const double *d_slab_outvec, double *d_outvec, int64_t ov_stride,
+                   void *stream);
+/* on a slab step, mod(t_next * timestep, timestep_slab) == 0: every member's ring mean,
+ * sml_res_step_members on the slab context, the new sst into the members' exchange rows,
+ * every member marked changed, *predicted (may be NULL) = 1; nothing otherwise */
+int sml_slab_predict(sml_slab *s, int64_t t_next, double *d_outvec, int64_t ov_stride, void *stream,
+                     int *predicted);
+/* if any member's sst changed: the E wholegrid_sst grids from the exchange rows and the sst
+ * entries of the E feedbacks; *wrote (may be NULL) reports it */
+int sml_slab_sst(sml_slab *s, const double *d_outvec, int64_t ov_stride, double *d_feedback, int64_t fb_stride,
+                 void *stream, int *wrote);
+/* column mod(t - 1, ring columns) of every member's ring from the E feedbacks */
+int sml_slab_ring(sml_slab *s, int64_t t, const double *d_feedback, int64_t fb_stride, void *stream);
+/* device views with their member strides in doubles: wholegrid_sst(96, 48), the ring
+ * [ring columns][ring_len], the last slab feedback [ring_len], the slab outvecs
+ * [nslab][resx*resy]; any may be NULL */
+int sml_slab_buffers(const sml_slab *s, const double **d_sst_grid, int64_t *sst_stride, const double **d_ring,
+                     int64_t *ring_stride, const double **d_slab_feedback, int64_t *fb_stride,
+                     const double **d_slab_outvec, int64_t *ov_stride);
 /* the two cross-stream dependencies of the overlapped loop: SML_HOP_WAIT_VALUE (a
  * sequence number written by the producer's stream, waited for by the consumer's, as
  * CP stream memory operations), SML_HOP_EVENTS (event record + wait), SML_HOP_KERNEL

@@ -35,6 +35,8 @@
 
 #include "sml_devmem.hpp"
 #include "sml_internal.hpp"
+#include "sml_slab.hpp"
+#include "sml_slab_layout.hpp"
 #include "sml_timeline.hpp"
 
 SML_TL_DEFINE(hybrid)
@@ -162,64 +164,6 @@ __global__ void k_gather_rows(const double *__restrict__ recv, const int32_t *__
     if (e >= total) return;
     const int r = e / nout, o = e % nout;
     glob[e] = recv[(size_t)perm[r] * nout + o];
-}
-
-// ---- slab ocean kernels (mpires.f90:288-478, 575-767)
-// the slab feedback: the mean of the ring of the last timestep_slab/timestep - 1 atmo
-// feedback subsets, summed column by column as Fortran's sum(.., dim=2) (mpires.f90:757)
-__global__ void k_slab_avg(const double *__restrict__ ring, int ncol, int tot, double *__restrict__ fb) {
-    const int e = blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= tot) return;
-    double s = 0.0;
-    for (int c = 0; c < ncol; ++c) s = s + ring[(size_t)c * tot + e];
-    fb[e] = s / (double)ncol;
-}
-
-// averaged_atmo_input_vec(:, col) = the atmo feedback at atmo_training_data_idx
-// (mpires.f90:755; the index list of trained_ocean_reservoir_prediction,
-// mod_slab_ocean_reservoir.f90:1550-1563)
-__global__ void k_slab_ring(const double *__restrict__ fb, const int32_t *__restrict__ src, int tot,
-                            double *__restrict__ col) {
-    const int e = blockIdx.x * blockDim.x + threadIdx.x;
-    if (e < tot) col[e] = fb[src[e]];
-}
-
-// the sst columns of the exchange rows: 272 for a region without a slab prediction
-// (mpires.f90:366-372), the slab outvec otherwise
-__global__ void k_slab_rows(const double *__restrict__ slab_ov, const int32_t *__restrict__ row, int nslab, int nsst,
-                            int nlocal, int nout, int xw, bool fill, double *__restrict__ ov) {
-    const int e = blockIdx.x * blockDim.x + threadIdx.x;
-    if (fill) {
-        if (e < nlocal * nsst) ov[(size_t)(e / nsst) * xw + nout + e % nsst] = 272.0;
-        return;
-    }
-    if (e < nslab * nsst) ov[(size_t)row[e / nsst] * xw + nout + e % nsst] = slab_ov[e];
-}
-
-// wholegrid_sst from every region's sst columns (tile_full_2d_grid_with_local_res,
-// res_domain.f90), land / permanent ice to base_sst_grid, floor 272 K
-// (mpires.f90:458-472; train_on_sst_anomalies off)
-__global__ void k_sst_grid(const double *__restrict__ ov_all, const int32_t *__restrict__ src,
-                           const double *__restrict__ base, const double *__restrict__ mask, double *__restrict__ sst) {
-    const int p = blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= kGrid2d) return;
-    double v = ov_all[src[p]];
-    if (mask[p] > 0.0) v = base[p];
-    if (v < 272.0) v = 272.0;
-    sst[p] = v;
-}
-
-// the atmo feedback's sst entries: the overlap tile of wholegrid_sst standardized with
-// the slab reservoir's sst mean / std (tile_4d_and_logp_to_local_state_input_slab +
-// standardize_data_given_pars1d, mpires.f90:575-581, copied over at :733-736)
-__global__ void k_sst_feedback(const double *__restrict__ sst, const int32_t *__restrict__ fbi,
-                               const int32_t *__restrict__ gi, const uint16_t *__restrict__ reg,
-                               const double *__restrict__ ms, int n, double *__restrict__ fb) {
-    const int e = blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= n) return;
-    const int j = reg[e];
-    const double t = sst[gi[e]] - ms[2 * j];
-    fb[fbi[e]] = t / ms[2 * j + 1];
 }
 
 }  // namespace
@@ -866,13 +810,11 @@ int slab_predict(sml_hybrid *h) {
     sl.dirty = true;
     if (sl.nslab == 0) return SML_OK;
     hipStream_t m = h->main;
-    hipLaunchKernelGGL(k_slab_avg, dim3((sl.tot_fb + 255) / 256), dim3(256), 0, m, sl.d_ring, sl.ratio - 1, sl.tot_fb,
-                       sl.d_fb);
+    // (the stage kernels of sml_slab.hpp at one member)
+    launch_slab_avg(sl.d_ring, 0, sl.ratio - 1, sl.tot_fb, sl.d_fb, 0, 1, m);
     SML_HIP(hipGetLastError());
     if (int rc = sml_res_step(sl.res, sl.d_fb, nullptr, sl.d_ov, m)) return rc;
-    const int n = sl.nslab * sl.nsst;
-    hipLaunchKernelGGL(k_slab_rows, dim3((n + 255) / 256), dim3(256), 0, m, sl.d_ov, sl.d_row, sl.nslab, sl.nsst,
-                       h->nlocal, h->nout, h->xw, false, h->ov);
+    launch_slab_rows(sl.d_ov, 0, sl.d_row, sl.nslab, sl.nsst, h->nlocal, h->nout, h->xw, h->ov, 0, 1, m);
     SML_HIP(hipGetLastError());
     return SML_OK;
 }
@@ -883,12 +825,10 @@ int slab_predict(sml_hybrid *h) {
 int slab_sst(sml_hybrid *h, const double *d_all, hipStream_t m) {
     sml_hybrid::Slab &sl = h->slab;
     if (!sl.res || !sl.dirty) return SML_OK;
-    hipLaunchKernelGGL(k_sst_grid, dim3((kGrid2d + 255) / 256), dim3(256), 0, m, d_all, sl.d_sst_src, sl.base, sl.mask,
-                       sl.d_sst);
+    launch_sst_grid(d_all, 0, sl.d_sst_src, sl.base, sl.mask, sl.d_sst, 0, 1, m);
     SML_HIP(hipGetLastError());
     if (sl.n_sst_el) {
-        hipLaunchKernelGGL(k_sst_feedback, dim3((sl.n_sst_el + 255) / 256), dim3(256), 0, m, sl.d_sst, sl.d_sfb,
-                           sl.d_sgrid, sl.d_sreg, sl.d_ms, sl.n_sst_el, h->fb);
+        launch_sst_feedback(sl.d_sst, 0, sl.d_sfb, sl.d_sgrid, sl.d_sreg, sl.d_ms, sl.n_sst_el, h->fb, 0, 1, m);
         SML_HIP(hipGetLastError());
     }
     if (int rc = sml_dyn_set_hybrid_sst(h->dyn, sl.d_sst, sl.sst_bias, m)) return rc;
@@ -912,64 +852,28 @@ extern "C" int sml_hybrid_set_slab(sml_hybrid *h, sml_reservoirs *slab, const do
     SML_REQUIRE(h && slab && d_base_sst && d_sea_mask, "null argument");
     SML_REQUIRE(!h->slab.res, "the slab ocean is set already");
     SML_REQUIRE(!h->ov, "sml_hybrid_set_slab must precede sml_hybrid_set_buffers (the exchange rows widen)");
-    SML_REQUIRE(timestep > 0 && timestep_slab % timestep == 0 && timestep_slab / timestep >= 2,
-                "timestep_slab (%d) must be a multiple >= 2 of timestep (%d)", timestep_slab, timestep);
+    if (int rc = check_slab_cadence(timestep, timestep_slab)) return rc;
     int snum = 0, nslab = 0, sncs = 0, snout = 0;
     if (int rc = sml_res_info(slab, &snum, &nslab, &sncs, &snout, nullptr)) return rc;
-    SML_REQUIRE(snum == h->numregions && sncs == 0, "the slab context must be ML-only (chunk_speedy 0) over the "
-                "same %d regions", h->numregions);
-    RegionGeom g0;
-    SML_REQUIRE(region_geom(h->numregions, 0, &g0) && snout == g0.resx * g0.resy,
-                "the slab reservoirs predict the sst of the region's %d points, not %d", g0.resx * g0.resy, snout);
-    std::vector<int> ids(h->nlocal), sids(nslab);
+    std::vector<int> ids(h->nlocal), sids(nslab), ninp(h->nlocal), sninp(nslab);
     std::vector<int64_t> off(h->nlocal + 1), soff(nslab + 1);
     if (int rc = sml_res_info(h->res, nullptr, nullptr, nullptr, nullptr, ids.data())) return rc;
     if (int rc = sml_res_info(slab, nullptr, nullptr, nullptr, nullptr, sids.data())) return rc;
     if (int rc = sml_res_feedback_offsets(h->res, off.data())) return rc;
     if (int rc = sml_res_feedback_offsets(slab, soff.data())) return rc;
-    // the slab reservoirs are those of the rank's regions with an sst input, in order
-    // (trained_ocean_reservoir_prediction: sst_bool_prediction <=> sst input)
-    std::vector<int32_t> ring_src, row, sfb, sgrid;
-    std::vector<uint16_t> sreg;
-    int j = 0;
-    for (int i = 0; i < h->nlocal; ++i) {
-        RegionGeom g;
-        region_geom(h->numregions, ids[i], &g);
-        const int in2d = g.inx * g.iny, natmo = kVars * in2d * kZGrid;
-        int ninp = 0;
-        if (int rc = sml_res_ninp(h->res, i, &ninp)) return rc;
-        const bool sst = ninp == region_ninp(g, true);
-        if (!sst) continue;
-        SML_REQUIRE(j < nslab && sids[j] == ids[i], "slab reservoir %d is not the rank's sst region %d (local %d)", j,
-                    ids[i], i);
-        int sninp = 0;
-        if (int rc = sml_res_ninp(slab, j, &sninp)) return rc;
-        SML_REQUIRE(sninp == 7 * in2d && soff[j + 1] - soff[j] == sninp,
-                    "slab reservoir of region %d: %d inputs, the atmo subset has %d", ids[i], sninp, 7 * in2d);
-        // atmo_training_data_idx (mod_slab_ocean_reservoir.f90:1550-1563): the lowest
-        // level's 4 variables and logp, the sst, the tisr of the atmo feedback
-        for (int e = natmo - kVars * in2d; e < natmo + in2d; ++e) ring_src.push_back((int32_t)(off[i] + e));
-        for (int e = natmo + 2 * in2d; e < natmo + 4 * in2d; ++e) ring_src.push_back((int32_t)(off[i] + e));
-        row.push_back(i);
-        for (int p = 0; p < in2d; ++p) {  // the sst entries of the atmo feedback
-            const int lx = p % g.inx, ly = p / g.inx;
-            sfb.push_back((int32_t)(off[i] + natmo + 2 * in2d + p));
-            sgrid.push_back(g2(input_x(g, lx + 1) - 1, g.in_ystart - 1 + ly));
-            sreg.push_back((uint16_t)j);
-        }
-        ++j;
-    }
-    SML_REQUIRE(j == nslab, "%d slab reservoirs for %d sst regions", nslab, j);
-    // wholegrid_sst point -> its region's exchange row and sst column
-    const int xw = h->nout + snout;
-    std::vector<int32_t> src(kGrid2d, -1);
-    for (int r = 0; r < h->numregions; ++r) {
-        RegionGeom g;
-        region_geom(h->numregions, r, &g);
-        for (int ly = 0; ly < g.resy; ++ly)
-            for (int lx = 0; lx < g.resx; ++lx)
-                src[g2(g.res_xstart - 1 + lx, g.res_ystart - 1 + ly)] = r * xw + h->nout + lx + g.resx * ly;
-    }
+    for (int i = 0; i < h->nlocal; ++i)
+        if (int rc = sml_res_ninp(h->res, i, &ninp[i])) return rc;
+    for (int j = 0; j < nslab; ++j)
+        if (int rc = sml_res_ninp(slab, j, &sninp[j])) return rc;
+    // the index tables and their consistency checks: host arithmetic (sml_slab_layout.cpp)
+    SlabTables tb;
+    if (int rc = build_slab_tables({h->numregions, h->nlocal, h->nout, ids.data(), ninp.data(), off.data(), snum, nslab,
+                                    sncs, snout, sids.data(), sninp.data(), soff.data()},
+                                   &tb))
+        return rc;
+    const std::vector<int32_t> &ring_src = tb.ring_src, &row = tb.row, &sfb = tb.sfb, &sgrid = tb.sgrid, &src = tb.src;
+    const std::vector<uint16_t> &sreg = tb.sreg;
+    const int xw = tb.xw;
     sml_hybrid::Slab &sl = h->slab;
     sl.nslab = nslab;
     sl.nsst = snout;
@@ -1025,13 +929,11 @@ extern "C" int sml_hybrid_start_slab(sml_hybrid *h, const double *d_slab_outvec)
     if (sl.nslab)  // (a rank without sst regions has no slab mean / std)
         SML_HIP(hipMemcpyAsync(sl.d_ms, ms.data(), (size_t)2 * sl.nslab * 8, hipMemcpyHostToDevice, m));
     SML_HIP(hipMemsetAsync(sl.d_ring, 0, (size_t)(sl.ratio - 1) * sl.tot_fb * 8, m));
-    const int nfill = h->nlocal * sl.nsst, n = sl.nslab * sl.nsst;
-    hipLaunchKernelGGL(k_slab_rows, dim3((nfill + 255) / 256), dim3(256), 0, m, nullptr, nullptr, 0, sl.nsst, h->nlocal,
-                       h->nout, h->xw, true, h->ov);
+    const int n = sl.nslab * sl.nsst;
+    launch_slab_fill(sl.nsst, h->nlocal, h->nout, h->xw, h->ov, 0, 1, m);
     if (n) {
         SML_HIP(hipMemcpyAsync(sl.d_ov, d_slab_outvec, (size_t)n * 8, hipMemcpyDeviceToDevice, m));
-        hipLaunchKernelGGL(k_slab_rows, dim3((n + 255) / 256), dim3(256), 0, m, sl.d_ov, sl.d_row, sl.nslab, sl.nsst,
-                           h->nlocal, h->nout, h->xw, false, h->ov);
+        launch_slab_rows(sl.d_ov, 0, sl.d_row, sl.nslab, sl.nsst, h->nlocal, h->nout, h->xw, h->ov, 0, 1, m);
     }
     SML_HIP(hipGetLastError());
     SML_HIP(hipStreamSynchronize(m));
@@ -1196,8 +1098,7 @@ extern "C" int sml_hybrid_advance(sml_hybrid *h, const double *d_outvec_all) {
     if (h->slab.res && h->slab.tot_fb) {  // averaged_atmo_input_vec(:, mod(t-1, R-1)+1), mpires.f90:755
         sml_hybrid::Slab &sl = h->slab;
         double *col = sl.d_ring + (size_t)((h->t - 1) % (sl.ratio - 1)) * sl.tot_fb;
-        hipLaunchKernelGGL(k_slab_ring, dim3((sl.tot_fb + 255) / 256), dim3(256), 0, m, h->fb, sl.d_ring_src, sl.tot_fb,
-                           col);
+        launch_slab_ring(h->fb, 0, sl.d_ring_src, sl.tot_fb, col, 0, 1, m);
         SML_HIP(hipGetLastError());
     }
     if (hops) {

@@ -82,6 +82,65 @@ __global__ void k_tile_tisr(const int32_t *__restrict__ fbi, const int32_t *__re
     feedback[fbi[e]] = t / ms[kMeanStd + 33];
 }
 
+// ---- the two feedback tilings for the E members of an ensemble, one launch each: member
+// e's grids, precipitation and feedback start e * g4s / g2s / fbs doubles into their
+// arrays.  A thread reads its table entries and its mean / std once and serves every
+// member with them, kTileMem members' gathers in flight together; per member the two
+// operations are k_tile_feedback's / k_tile_tisr's.
+constexpr int kTileMem = 4;
+
+__global__ void k_tile_feedback_mem(const int32_t *__restrict__ src, const uint8_t *__restrict__ lidx,
+                                    const uint16_t *__restrict__ reg, const double *__restrict__ meanstd,
+                                    const double *__restrict__ g4, const double *__restrict__ g2,
+                                    const double *__restrict__ pr, const double *__restrict__ tisr,
+                                    double *__restrict__ feedback, int total, int E, int64_t g4s, int64_t g2s,
+                                    int64_t fbs) {
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= total) return;
+    const int s = src[e];
+    if (s == kSrcKeep) return;
+    if (s < kSrcKeep) {  // tisr entry: -2 - packed index; the vector is the members' common one
+        if (tisr) {
+            const double v = tisr[-2 - s];
+            for (int m = 0; m < E; ++m) feedback[(size_t)m * fbs + e] = v;
+        }
+        return;
+    }
+    const double *ms = meanstd + (size_t)reg[e] * 2 * kMeanStd;
+    const int l = lidx[e];
+    const double mean = ms[l], stdv = ms[kMeanStd + l];
+    // which grid, and where in it: the same for every member
+    const double *g = s < kGrid4d ? g4 : s < kGrid4d + kGrid2d ? g2 : pr;
+    const int64_t gs = s < kGrid4d ? g4s : g2s;
+    const int at = s < kGrid4d ? s : s < kGrid4d + kGrid2d ? s - kGrid4d : s - kGrid4d - kGrid2d;
+    for (int m0 = 0; m0 < E; m0 += kTileMem) {
+        double v[kTileMem];
+#pragma unroll
+        for (int k = 0; k < kTileMem; ++k)
+            if (m0 + k < E) v[k] = g[(size_t)(m0 + k) * gs + at];
+#pragma unroll
+        for (int k = 0; k < kTileMem; ++k)
+            if (m0 + k < E) {
+                const double t = v[k] - mean;
+                feedback[(size_t)(m0 + k) * fbs + e] = t / stdv;
+            }
+    }
+}
+
+// one hour's tisr field into the E feedbacks (the members share the date)
+__global__ void k_tile_tisr_mem(const int32_t *__restrict__ fbi, const int32_t *__restrict__ gi,
+                                const uint16_t *__restrict__ reg, const double *__restrict__ meanstd,
+                                const double *__restrict__ G, double *__restrict__ feedback, int total, int E,
+                                int64_t fbs) {
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= total) return;
+    const double *ms = meanstd + (size_t)reg[e] * 2 * kMeanStd;
+    const double t = G[gi[e]] - ms[33];
+    const double v = t / ms[kMeanStd + 33];
+    const int d = fbi[e];
+    for (int m = 0; m < E; ++m) feedback[(size_t)m * fbs + d] = v;
+}
+
 // tile local_model: SPEEDY forecast at the region's own points, standardized
 __global__ void k_tile_local_model(const int32_t *__restrict__ src, const uint8_t *__restrict__ lidx,
                                    const double *__restrict__ meanstd, const double *__restrict__ fc4,

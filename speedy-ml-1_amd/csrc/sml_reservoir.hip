@@ -1611,6 +1611,45 @@ extern "C" int sml_res_tile_tisr_field(sml_reservoirs *c, const double *d_tisr_g
     return SML_OK;
 }
 
+// the two feedback tilings for every member of the context, one launch each (at one member:
+// the single-member calls)
+extern "C" int sml_res_tile_feedback_members(sml_reservoirs *c, const double *d_grid4d, int64_t g4_stride,
+                                             const double *d_grid2d, const double *d_precip, int64_t g2_stride,
+                                             const double *d_tisr, double *d_feedback, int64_t fb_stride,
+                                             void *stream) {
+    SML_REQUIRE(c && d_grid4d && d_grid2d && d_precip && d_feedback, "null argument");
+    SML_REQUIRE(!c->generic, "a generic (slab) context has no exchange tables");
+    SML_REQUIRE(g4_stride >= kGrid4d, "g4_stride %lld smaller than the 4-d grid's %d doubles", (long long)g4_stride,
+                kGrid4d);
+    SML_REQUIRE(g2_stride >= kGrid2d, "g2_stride %lld smaller than the 2-d grid's %d doubles", (long long)g2_stride,
+                kGrid2d);
+    if (int rc = check_fb_stride(c, fb_stride)) return rc;
+    if (c->members == 1) return sml_res_tile_feedback(c, d_grid4d, d_grid2d, d_precip, d_tisr, d_feedback, stream);
+    if (c->tot_fb) {
+        const int total = (int)c->tot_fb;
+        hipLaunchKernelGGL(k_tile_feedback_mem, dim3((total + 255) / 256), dim3(256), 0, (hipStream_t)stream,
+                           c->d_fb_src, c->d_fb_l, c->d_fb_reg, c->d_meanstd, d_grid4d, d_grid2d, d_precip, d_tisr,
+                           d_feedback, total, c->members, g4_stride, g2_stride, fb_stride);
+        SML_HIP(hipGetLastError());
+    }
+    return SML_OK;
+}
+
+extern "C" int sml_res_tile_tisr_field_members(sml_reservoirs *c, const double *d_tisr_grid, double *d_feedback,
+                                               int64_t fb_stride, void *stream) {
+    SML_REQUIRE(c && d_tisr_grid && d_feedback, "null argument");
+    SML_REQUIRE(!c->generic, "a generic (slab) context has no exchange tables");
+    if (int rc = check_fb_stride(c, fb_stride)) return rc;
+    if (c->members == 1) return sml_res_tile_tisr_field(c, d_tisr_grid, d_feedback, stream);
+    if (c->tot_tisr) {
+        hipLaunchKernelGGL(k_tile_tisr_mem, dim3((c->tot_tisr + 255) / 256), dim3(256), 0, (hipStream_t)stream,
+                           c->d_tisr_fb, c->d_tisr_grid, c->d_tisr_reg, c->d_meanstd, d_tisr_grid, d_feedback,
+                           c->tot_tisr, c->members, fb_stride);
+        SML_HIP(hipGetLastError());
+    }
+    return SML_OK;
+}
+
 extern "C" int sml_res_tile_local_model(sml_reservoirs *c, const double *d_fc4d, const double *d_fc2d,
                                         double *d_local_model, void *stream) {
     SML_REQUIRE(c && d_fc4d && d_fc2d && d_local_model, "null argument");

@@ -1,0 +1,263 @@
+// sml_slab.hip -- the slab ocean of an E-member forecast on one rank: the slab reservoirs'
+// step for every member through one stream of their weights (sml_res_step_members) and
+// sendrecievegrid's sst half (mpires.f90:288-478, 575-767) with a member dimension, one
+// launch per stage (sml_slab.hpp).  Per member it is the slab ocean of the single-member
+// loop (sml_hybrid_set_slab / sml_hybrid_start_slab and the slab stages of
+// sml_hybrid_predict / sml_hybrid_advance), bit for bit; the host strings the calls
+// together in that loop's order (speedy_ml_amd.ensemble.EnsembleLoop).
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <new>
+#include <vector>
+
+#include "sml_devmem.hpp"
+#include "sml_internal.hpp"
+#include "sml_slab.hpp"
+#include "sml_slab_layout.hpp"
+
+using namespace sml;
+
+struct sml_slab {
+    DevMem mem;  // first: every device buffer below is its
+    sml_reservoirs *atmo = nullptr, *res = nullptr;
+    int E = 1, nlocal = 0, nout = 0, xw = 0;
+    int nslab = 0, nsst = 4, ratio = 28, tot_fb = 0, n_sst_el = 0;
+    int timestep = 6, timestep_slab = 168;
+    double sst_bias = 0.0;  // current_sst_bias, for each member's sml_dyn_set_hybrid_sst
+    const double *base = nullptr, *mask = nullptr;  // base_sst_grid, sea_mask (96, 48)
+    // per member, packed: the slab feedback [tot_fb], the slab outvecs [nslab][nsst], the
+    // ring [ratio - 1][tot_fb], wholegrid_sst [96 * 48]; the slabs' sst mean / std [nslab][2]
+    double *d_fb = nullptr, *d_ov = nullptr, *d_ring = nullptr, *d_sst = nullptr, *d_ms = nullptr;
+    int32_t *d_ring_src = nullptr, *d_row = nullptr, *d_sst_src = nullptr, *d_sfb = nullptr, *d_sgrid = nullptr;
+    uint16_t *d_sreg = nullptr;
+    std::vector<char> started;  // per member
+    bool dirty = false, ms_set = false;
+    int64_t fb_stride() const { return std::max(tot_fb, 1); }
+    int64_t ov_stride() const { return std::max(nslab * nsst, 1); }
+    int64_t ring_stride() const { return std::max<int64_t>((int64_t)(ratio - 1) * tot_fb, 1); }
+};
+
+namespace {
+
+template <typename T>
+int upload(sml_slab *s, T **d, const std::vector<T> &v) {
+    if (s->mem.device(d, std::max<size_t>(v.size(), 1), false)) return fail(SML_ERR_NOMEM, "slab tables");
+    if (!v.empty()) SML_HIP(hipMemcpy(*d, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
+    return SML_OK;
+}
+
+int create_impl(sml_slab *s, const double *d_base_sst, const double *d_sea_mask, int timestep, int timestep_slab) {
+    int numregions = 0, snum = 0, sncs = 0, snout = 0, sE = 0;
+    if (int rc = sml_res_info(s->atmo, &numregions, &s->nlocal, nullptr, &s->nout, nullptr)) return rc;
+    if (int rc = sml_res_info(s->res, &snum, &s->nslab, &sncs, &snout, nullptr)) return rc;
+    if (int rc = sml_res_members(s->atmo, &s->E)) return rc;
+    if (int rc = sml_res_members(s->res, &sE)) return rc;
+    SML_REQUIRE(sE == s->E, "the slab context holds %d members, the atmo context %d (sml_res_set_members)", sE, s->E);
+    SML_REQUIRE(res_in_global_order(s->atmo), "the atmo context must hold every region, in global order (one rank)");
+    const int nlocal = s->nlocal, nslab = s->nslab;
+    std::vector<int> ids(nlocal), sids(nslab), ninp(nlocal), sninp(nslab);
+    std::vector<int64_t> off(nlocal + 1), soff(nslab + 1);
+    if (int rc = sml_res_info(s->atmo, nullptr, nullptr, nullptr, nullptr, ids.data())) return rc;
+    if (int rc = sml_res_info(s->res, nullptr, nullptr, nullptr, nullptr, sids.data())) return rc;
+    if (int rc = sml_res_feedback_offsets(s->atmo, off.data())) return rc;
+    if (int rc = sml_res_feedback_offsets(s->res, soff.data())) return rc;
+    for (int i = 0; i < nlocal; ++i)
+        if (int rc = sml_res_ninp(s->atmo, i, &ninp[i])) return rc;
+    for (int j = 0; j < nslab; ++j)
+        if (int rc = sml_res_ninp(s->res, j, &sninp[j])) return rc;
+    SlabTables tb;
+    if (int rc = build_slab_tables({numregions, nlocal, s->nout, ids.data(), ninp.data(), off.data(), snum, nslab, sncs,
+                                    snout, sids.data(), sninp.data(), soff.data()},
+                                   &tb))
+        return rc;
+    s->nsst = snout;
+    s->ratio = timestep_slab / timestep;
+    s->timestep = timestep;
+    s->timestep_slab = timestep_slab;
+    s->base = d_base_sst;
+    s->mask = d_sea_mask;
+    s->tot_fb = (int)tb.ring_src.size();
+    s->n_sst_el = (int)tb.sfb.size();
+    s->xw = tb.xw;
+    if (int rc = upload(s, &s->d_ring_src, tb.ring_src)) return rc;
+    if (int rc = upload(s, &s->d_row, tb.row)) return rc;
+    if (int rc = upload(s, &s->d_sst_src, tb.src)) return rc;
+    if (int rc = upload(s, &s->d_sfb, tb.sfb)) return rc;
+    if (int rc = upload(s, &s->d_sgrid, tb.sgrid)) return rc;
+    if (int rc = upload(s, &s->d_sreg, tb.sreg)) return rc;
+    const size_t E = (size_t)s->E;
+    s->mem.device(&s->d_fb, E * s->fb_stride());
+    s->mem.device(&s->d_ov, E * s->ov_stride());
+    s->mem.device(&s->d_ring, E * s->ring_stride());
+    s->mem.device(&s->d_sst, E * kGrid2d);
+    s->mem.device(&s->d_ms, std::max<size_t>((size_t)2 * nslab, 1));
+    if (s->mem.status()) return fail(SML_ERR_NOMEM, "slab buffers");
+    s->started.assign(s->E, 0);
+    return sml_res_set_outvec_ld(s->atmo, s->xw);
+}
+
+// the members' atmo outvecs [E][nlocal][xw] and feedbacks [E][>= the packed feedback]
+int check_ov_stride(const sml_slab *s, int64_t ov_stride) {
+    SML_REQUIRE(ov_stride >= (int64_t)s->nlocal * s->xw, "ov_stride %lld smaller than nlocal * the exchange width %d",
+                (long long)ov_stride, s->xw);
+    return SML_OK;
+}
+int check_fb_stride(const sml_slab *s, int64_t fb_stride) {
+    std::vector<int64_t> off(s->nlocal + 1);
+    if (int rc = sml_res_feedback_offsets(s->atmo, off.data())) return rc;
+    SML_REQUIRE(fb_stride >= off[s->nlocal], "fb_stride %lld smaller than the packed feedback size %lld",
+                (long long)fb_stride, (long long)off[s->nlocal]);
+    return SML_OK;
+}
+
+}  // namespace
+
+extern "C" int sml_slab_create(sml_reservoirs *atmo, sml_reservoirs *slab, const double *d_base_sst,
+                               const double *d_sea_mask, int timestep, int timestep_slab, double sst_bias,
+                               sml_slab **out) {
+    SML_REQUIRE(out, "null argument");
+    *out = nullptr;
+    SML_REQUIRE(atmo && slab && d_base_sst && d_sea_mask, "null argument");
+    if (int rc = check_slab_cadence(timestep, timestep_slab)) return rc;
+    sml_slab *s = new (std::nothrow) sml_slab();
+    if (!s) return fail(SML_ERR_NOMEM, "host allocation failed");
+    s->atmo = atmo;
+    s->res = slab;
+    s->sst_bias = sst_bias;
+    if (int rc = create_impl(s, d_base_sst, d_sea_mask, timestep, timestep_slab)) {
+        delete s;
+        return rc;
+    }
+    *out = s;
+    return SML_OK;
+}
+
+extern "C" int sml_slab_destroy(sml_slab *s) {
+    if (!s) return SML_OK;
+    (void)hipDeviceSynchronize();
+    delete s;
+    return SML_OK;
+}
+
+extern "C" int sml_slab_info(const sml_slab *s, int *members, int *exchange_width, int *nslab, int *ring_columns,
+                             int *ring_len, double *sst_bias) {
+    SML_REQUIRE(s, "null context");
+    if (members) *members = s->E;
+    if (exchange_width) *exchange_width = s->xw;
+    if (nslab) *nslab = s->nslab;
+    if (ring_columns) *ring_columns = s->ratio - 1;
+    if (ring_len) *ring_len = s->tot_fb;
+    if (sst_bias) *sst_bias = s->sst_bias;
+    return SML_OK;
+}
+
+// start_prediction_slab's hand-over for one member (sml_hybrid_start_slab): 272 K in every
+// sst column of the member's exchange rows, its slab outvecs over them, its ring cleared
+extern "C" int sml_slab_start(sml_slab *s, int member, const double *d_slab_outvec, double *d_outvec,
+                              int64_t ov_stride, void *stream) {
+    SML_REQUIRE(s && d_outvec, "null argument");
+    SML_REQUIRE(member >= 0 && member < s->E, "member %d out of range [0, %d)", member, s->E);
+    SML_REQUIRE(s->nslab == 0 || d_slab_outvec, "null slab outvec");
+    if (int rc = check_ov_stride(s, ov_stride)) return rc;
+    hipStream_t m = (hipStream_t)stream;
+    if (!s->ms_set && s->nslab) {  // once: the weights are loaded by now, and the same for every member
+        std::vector<double> ms(2 * (size_t)s->nslab);
+        for (int j = 0; j < s->nslab; ++j) {
+            double mean[36], stdv[36];
+            if (int rc = sml_res_mean_std(s->res, j, mean, stdv)) return rc;
+            ms[2 * j] = mean[35];  // sst_mean_std_idx = the atmo grid's, 36 (mod_slab_ocean_reservoir.f90:1548)
+            ms[2 * j + 1] = stdv[35];
+        }
+        SML_HIP(hipMemcpy(s->d_ms, ms.data(), ms.size() * 8, hipMemcpyHostToDevice));
+        s->ms_set = true;
+    }
+    double *ov = d_outvec + (size_t)member * ov_stride;
+    double *sov = s->d_ov + (size_t)member * s->ov_stride();
+    if (s->tot_fb)
+        SML_HIP(hipMemsetAsync(s->d_ring + (size_t)member * s->ring_stride(), 0,
+                               (size_t)(s->ratio - 1) * s->tot_fb * 8, m));
+    const int n = s->nslab * s->nsst;
+    if (s->nlocal) launch_slab_fill(s->nsst, s->nlocal, s->nout, s->xw, ov, 0, 1, m);
+    if (n) {
+        SML_HIP(hipMemcpyAsync(sov, d_slab_outvec, (size_t)n * 8, hipMemcpyDeviceToDevice, m));
+        launch_slab_rows(sov, 0, s->d_row, s->nslab, s->nsst, s->nlocal, s->nout, s->xw, ov, 0, 1, m);
+    }
+    SML_HIP(hipGetLastError());
+    SML_HIP(hipStreamSynchronize(m));
+    s->dirty = true;
+    s->started[member] = 1;
+    return SML_OK;
+}
+
+// predict_slab_ml of every member on a slab step (parallelmain.f90:236-249:
+// mod(t_next * timestep, timestep_slab) == 0), nothing on the others
+extern "C" int sml_slab_predict(sml_slab *s, int64_t t_next, double *d_outvec, int64_t ov_stride, void *stream,
+                                int *predicted) {
+    SML_REQUIRE(s && d_outvec && t_next >= 1, "bad argument");
+    if (predicted) *predicted = 0;
+    if (int rc = check_ov_stride(s, ov_stride)) return rc;
+    for (int e = 0; e < s->E; ++e)
+        if (!s->started[e]) return fail(SML_ERR_STATE, "sml_slab_start of member %d first", e);
+    if ((t_next * s->timestep) % s->timestep_slab != 0) return SML_OK;
+    s->dirty = true;
+    if (predicted) *predicted = 1;
+    if (s->nslab == 0) return SML_OK;
+    hipStream_t m = (hipStream_t)stream;
+    launch_slab_avg(s->d_ring, s->ring_stride(), s->ratio - 1, s->tot_fb, s->d_fb, s->fb_stride(), s->E, m);
+    SML_HIP(hipGetLastError());
+    if (int rc = sml_res_step_members(s->res, s->d_fb, s->fb_stride(), nullptr, 0, s->d_ov, s->ov_stride(), m))
+        return rc;
+    launch_slab_rows(s->d_ov, s->ov_stride(), s->d_row, s->nslab, s->nsst, s->nlocal, s->nout, s->xw, d_outvec,
+                     ov_stride, s->E, m);
+    SML_HIP(hipGetLastError());
+    return SML_OK;
+}
+
+// sendrecievegrid's sst half after a change of any member's slab sst: the E wholegrid_sst
+// grids from the exchange rows and the sst entries of the E atmo feedbacks
+extern "C" int sml_slab_sst(sml_slab *s, const double *d_outvec, int64_t ov_stride, double *d_feedback,
+                            int64_t fb_stride, void *stream, int *wrote) {
+    SML_REQUIRE(s && d_outvec && d_feedback, "null argument");
+    if (wrote) *wrote = 0;
+    if (int rc = check_ov_stride(s, ov_stride)) return rc;
+    if (int rc = check_fb_stride(s, fb_stride)) return rc;
+    if (!s->dirty) return SML_OK;
+    hipStream_t m = (hipStream_t)stream;
+    launch_sst_grid(d_outvec, ov_stride, s->d_sst_src, s->base, s->mask, s->d_sst, kGrid2d, s->E, m);
+    SML_HIP(hipGetLastError());
+    if (s->n_sst_el) {
+        launch_sst_feedback(s->d_sst, kGrid2d, s->d_sfb, s->d_sgrid, s->d_sreg, s->d_ms, s->n_sst_el, d_feedback,
+                            fb_stride, s->E, m);
+        SML_HIP(hipGetLastError());
+    }
+    s->dirty = false;
+    if (wrote) *wrote = 1;
+    return SML_OK;
+}
+
+// averaged_atmo_input_vec(:, mod(t-1, R-1)+1) of every member from the E feedbacks (mpires.f90:755)
+extern "C" int sml_slab_ring(sml_slab *s, int64_t t, const double *d_feedback, int64_t fb_stride, void *stream) {
+    SML_REQUIRE(s && d_feedback && t >= 1, "bad argument");
+    if (int rc = check_fb_stride(s, fb_stride)) return rc;
+    if (!s->tot_fb) return SML_OK;
+    double *col = s->d_ring + (size_t)((t - 1) % (s->ratio - 1)) * s->tot_fb;
+    launch_slab_ring(d_feedback, fb_stride, s->d_ring_src, s->tot_fb, col, s->ring_stride(), s->E, (hipStream_t)stream);
+    SML_HIP(hipGetLastError());
+    return SML_OK;
+}
+
+extern "C" int sml_slab_buffers(const sml_slab *s, const double **d_sst_grid, int64_t *sst_stride,
+                                const double **d_ring, int64_t *ring_stride, const double **d_slab_feedback,
+                                int64_t *fb_stride, const double **d_slab_outvec, int64_t *ov_stride) {
+    SML_REQUIRE(s, "null context");
+    if (d_sst_grid) *d_sst_grid = s->d_sst;
+    if (sst_stride) *sst_stride = kGrid2d;
+    if (d_ring) *d_ring = s->d_ring;
+    if (ring_stride) *ring_stride = s->ring_stride();
+    if (d_slab_feedback) *d_slab_feedback = s->d_fb;
+    if (fb_stride) *fb_stride = s->fb_stride();
+    if (d_slab_outvec) *d_slab_outvec = s->d_ov;
+    if (ov_stride) *ov_stride = s->ov_stride();
+    return SML_OK;
+}

@@ -579,6 +579,84 @@ module sml_hip
       integer(c_int), intent(out) :: ring_len
       integer(c_int) :: rc
     end function
+    !> the feedback tilings for every member of the context, one launch each: member e's
+    !> grids and feedback e * stride doubles into their arrays
+    function sml_res_tile_feedback_members(ctx, d_grid4d, g4_stride, d_grid2d, d_precip, g2_stride, d_tisr, &
+        d_feedback, fb_stride, stream) bind(C, name='sml_res_tile_feedback_members') result(rc)
+      import :: c_ptr, c_int, c_int64_t
+      type(c_ptr), value :: ctx, d_grid4d, d_grid2d, d_precip, d_tisr, d_feedback, stream
+      integer(c_int64_t), value :: g4_stride, g2_stride, fb_stride
+      integer(c_int) :: rc
+    end function
+    function sml_res_tile_tisr_field_members(ctx, d_tisr_grid, d_feedback, fb_stride, stream) &
+        bind(C, name='sml_res_tile_tisr_field_members') result(rc)
+      import :: c_ptr, c_int, c_int64_t
+      type(c_ptr), value :: ctx, d_tisr_grid, d_feedback, stream
+      integer(c_int64_t), value :: fb_stride
+      integer(c_int) :: rc
+    end function
+    !> the slab ocean of an E-member forecast: sendrecievegrid's sst half with a member
+    !> dimension (include/speedy_ml.h, sml_slab_*)
+    function sml_slab_create(atmo, slab, d_base_sst, d_sea_mask, timestep, timestep_slab, sst_bias, s) &
+        bind(C, name='sml_slab_create') result(rc)
+      import :: c_ptr, c_int, c_double
+      type(c_ptr), value :: atmo, slab, d_base_sst, d_sea_mask
+      integer(c_int), value :: timestep, timestep_slab
+      real(c_double), value :: sst_bias
+      type(c_ptr), intent(out) :: s
+      integer(c_int) :: rc
+    end function
+    function sml_slab_destroy(s) bind(C, name='sml_slab_destroy') result(rc)
+      import :: c_ptr, c_int
+      type(c_ptr), value :: s
+      integer(c_int) :: rc
+    end function
+    function sml_slab_info(s, members, exchange_width, nslab, ring_columns, ring_len, sst_bias) &
+        bind(C, name='sml_slab_info') result(rc)
+      import :: c_ptr, c_int, c_double
+      type(c_ptr), value :: s
+      integer(c_int), intent(out) :: members, exchange_width, nslab, ring_columns, ring_len
+      real(c_double), intent(out) :: sst_bias
+      integer(c_int) :: rc
+    end function
+    function sml_slab_start(s, member, d_slab_outvec, d_outvec, ov_stride, stream) &
+        bind(C, name='sml_slab_start') result(rc)
+      import :: c_ptr, c_int, c_int64_t
+      type(c_ptr), value :: s, d_slab_outvec, d_outvec, stream
+      integer(c_int), value :: member
+      integer(c_int64_t), value :: ov_stride
+      integer(c_int) :: rc
+    end function
+    function sml_slab_predict(s, t_next, d_outvec, ov_stride, stream, predicted) &
+        bind(C, name='sml_slab_predict') result(rc)
+      import :: c_ptr, c_int, c_int64_t
+      type(c_ptr), value :: s, d_outvec, stream
+      integer(c_int64_t), value :: t_next, ov_stride
+      integer(c_int), intent(out) :: predicted
+      integer(c_int) :: rc
+    end function
+    function sml_slab_sst(s, d_outvec, ov_stride, d_feedback, fb_stride, stream, wrote) &
+        bind(C, name='sml_slab_sst') result(rc)
+      import :: c_ptr, c_int, c_int64_t
+      type(c_ptr), value :: s, d_outvec, d_feedback, stream
+      integer(c_int64_t), value :: ov_stride, fb_stride
+      integer(c_int), intent(out) :: wrote
+      integer(c_int) :: rc
+    end function
+    function sml_slab_ring(s, t, d_feedback, fb_stride, stream) bind(C, name='sml_slab_ring') result(rc)
+      import :: c_ptr, c_int, c_int64_t
+      type(c_ptr), value :: s, d_feedback, stream
+      integer(c_int64_t), value :: t, fb_stride
+      integer(c_int) :: rc
+    end function
+    function sml_slab_buffers(s, d_sst_grid, sst_stride, d_ring, ring_stride, d_slab_feedback, fb_stride, &
+        d_slab_outvec, ov_stride) bind(C, name='sml_slab_buffers') result(rc)
+      import :: c_ptr, c_int, c_int64_t
+      type(c_ptr), value :: s
+      type(c_ptr), intent(out) :: d_sst_grid, d_ring, d_slab_feedback, d_slab_outvec
+      integer(c_int64_t), intent(out) :: sst_stride, ring_stride, fb_stride, ov_stride
+      integer(c_int) :: rc
+    end function
     !> advance from the host's all-gather output d_recv(nout, maxc, world)
     function sml_hybrid_advance_slabs(h, d_recv) bind(C, name='sml_hybrid_advance_slabs') result(rc)
       import :: c_ptr, c_int

@@ -69,6 +69,9 @@ EXPORTED = (
     "sml_res_step_members", "sml_res_synchronize_members", "sml_res_member_tile",
     "sml_res_step_begin_members", "sml_res_step_finish_members", "sml_res_step_finish_grid_members",
     "sml_res_step_finish_assemble_members", "sml_res_member_finish_tile",
+    "sml_res_tile_feedback_members", "sml_res_tile_tisr_field_members",
+    "sml_slab_create", "sml_slab_destroy", "sml_slab_info", "sml_slab_start", "sml_slab_predict", "sml_slab_sst",
+    "sml_slab_ring", "sml_slab_buffers",
 )
 
 SML_HOP_AUTO, SML_HOP_WAIT_VALUE, SML_HOP_EVENTS, SML_HOP_KERNEL = 0, 1, 2, 3
@@ -290,6 +293,16 @@ def _declare(L: ctypes.CDLL) -> None:
         "sml_res_step_finish_grid_members": [vp, vp, i64, vp, i64, vp, i64, vp, i64, vp],
         "sml_res_step_finish_assemble_members": [vp, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, vp, i64, vp],
         "sml_res_member_finish_tile": [vp, ip],
+        "sml_res_tile_feedback_members": [vp, vp, i64, vp, vp, i64, vp, vp, i64, vp],
+        "sml_res_tile_tisr_field_members": [vp, vp, vp, i64, vp],
+        "sml_slab_create": [vp, vp, vp, vp, i, i, d, pp],
+        "sml_slab_destroy": [vp],
+        "sml_slab_info": [vp, ip, ip, ip, ip, ip, ctypes.POINTER(ctypes.c_double)],
+        "sml_slab_start": [vp, i, vp, vp, i64, vp],
+        "sml_slab_predict": [vp, i64, vp, i64, vp, ip],
+        "sml_slab_sst": [vp, vp, i64, vp, i64, vp, ip],
+        "sml_slab_ring": [vp, i64, vp, i64, vp],
+        "sml_slab_buffers": [vp, pp, i64p, pp, i64p, pp, i64p, pp, i64p],
     }
     for name, args in sig.items():
         if os.environ.get("SML_LIB") and not hasattr(L, name):

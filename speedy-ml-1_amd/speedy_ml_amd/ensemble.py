@@ -9,39 +9,52 @@ the reservoir's CUs while the E windows run one after the other on SPEEDY's, and
 finish (finish_assemble_members: local models tiled from the E forecasts, the members' outvecs,
 the E assembled grids) waits for the forecasts.
 
-Schedule of step():
-  main stream  finish_assemble_members(f4, f2 -> lm, ov, g4, g2, pr)
-               tile_feedback per member into fb[e]                      -> event
+Schedule of step(), in the order of the native loop's predict and advance (sml_hybrid.hip), so
+that every member is that loop:
+  host         the date of step t + 1, then the tisr table's hour of step t (in that order:
+               the two share the calendar's February latch), once for all members
+  main stream  the slab ocean's predict on a slab step (sml_slab_predict: the E ring means,
+               the slab reservoirs' step for all members, the new sst into the exchange rows)
+               finish_assemble_members(f4, f2 -> lm, ov, g4, g2, pr)
+               after a change of the slab sst: the E wholegrid_sst grids and the feedbacks'
+               sst entries (sml_slab_sst), each grid into its member's window (set_hybrid_sst)
+               tile_feedback_members into fb, the table's tisr field (tile_tisr_field_members),
+               the slab ring's column (sml_slab_ring): one launch each        -> event
                begin_members(fb): the next step's update and v_ml (the states run one update
                ahead, as the pipelined HybridLoop's do; cancel_step() rolls them back)
-  side stream  waits for the event, then for e = 0 .. E - 1: dyns[e].run_model(g4[e], g2[e] ->
-               f4[e], f2[e]); the host waits for window e (its safety flag, then the stream)
-               before it enqueues window e + 1.
+  side stream  waits for the event, then for e = 0 .. E - 1: dyns[e].fordate(date) with the
+               calendar on, dyns[e].run_model(g4[e], g2[e] -> f4[e], f2[e]); the host waits
+               for window e (its safety flag, then the stream) before it enqueues window e + 1.
 That host wait is a safety rule, not a convenience: every Dynamics has a check stream whose
 kernel polls in-kernel, an in-kernel wait holds its hardware queue, and
 the E contexts' streams share the process's few queues -- so no window is enqueued while
 another context's window or check is outstanding.
 
+The slab ocean (`slab=`), run_model's calendar (set_calendar) and get_tisr_by_date
+(set_tisr_table) are HybridLoop's, with the same refusals.
+
 Out of scope here: more than one rank (world > 1: `res` holds every region in global order),
-the slab ocean, the calendar and the tisr table (a fixed tisr or none), concurrent windows, and
-a native (sml_hybrid_*) form of this loop.
+concurrent windows, and a native (sml_hybrid_*) form of this loop.
 """
 from __future__ import annotations
 
 import ctypes
 import os
 
+import numpy as np
 import torch
 
-from ._lib import check, lib
+from ._lib import SmlError, check, lib, ptr
 from .dynamics import ALPH, DELT
 
 
 class EnsembleLoop:
     """res: Reservoirs holding every region in global order with set_members(len(dyns))
     done; dyns: one Dynamics per member, each with its own state, forcing and physics;
-    tisr: [nlocal, 16] standardized tisr inputs (device) or None.  Owns the members'
-    strided buffers fb [E, tot], lm [E, nlocal, ncs], ov [E, nlocal, nout], g4 / f4
+    tisr: [nlocal, 16] standardized tisr inputs (device) or None; slab: None, or a SlabOcean
+    (speedy_ml_amd.hybrid) whose `res` has set_members(len(dyns)) done -- the exchange rows
+    then carry each region's slab sst beside its outvec.  Owns the members' strided buffers
+    fb [E, tot], lm [E, nlocal, ncs], ov [E, nlocal, exchange_width], g4 / f4
     [E, 8, 48, 96, 4], g2 / pr / f2 [E, 48, 96] and two library streams on the CU split
     HybridLoop uses: SPEEDY on CUs [0, speedy_cus), the reservoir on the rest.  As
     HybridLoop does, it moves each Dynamics' safety check to a CU-masked stream on the
@@ -51,13 +64,16 @@ class EnsembleLoop:
     other until the check's time-out)."""
 
     def __init__(self, res, dyns, device, tisr=None, nleap: int = 24, delt: float = DELT,
-                 speedy_cus: int | None = None):
-        self.res, self.dyns, self.tisr = res, list(dyns), tisr
+                 speedy_cus: int | None = None, slab=None):
+        self.res, self.dyns, self.tisr, self.slab = res, list(dyns), tisr, slab
+        self._slab_h = None
         self.E = len(self.dyns)
         if self.E < 1 or res.members != self.E:
             raise ValueError(f"dyns: {self.E} models for a context of {res.members} members (set_members first)")
         if res.nlocal != res.numregions or list(res.region_ids) != list(range(res.numregions)):
             raise ValueError("res: every region of the decomposition, in global order, expected (world 1)")
+        if slab is not None and slab.res.members != self.E:
+            raise ValueError(f"slab: a context of {slab.res.members} members for {self.E} models (set_members first)")
         self.nleap, self.delt = nleap, delt
         self.dev = torch.device(device)
         E, nl = self.E, res.nlocal
@@ -84,8 +100,38 @@ class EnsembleLoop:
                 self.speedy_cus = self.res_cus = 0
                 self.side, self.main = self._cu_stream(0, ncu), self._cu_stream(0, ncu)
         self._tiled = torch.cuda.Event()
-        self._started = set()
+        self._started, self._slab_started = set(), set()
         self._flags = [True] * E
+        # the steps done, and the calendar run_model's date and the tisr table share
+        self.t = 0
+        self._cal_on, self._table = False, None
+        self._startyear, self._base, self._step_hours, self._feb29 = 0, 0, 6, 0
+        self.exchange_width = res.nout
+        if slab is not None:
+            self._set_slab(slab)
+
+    def _set_slab(self, slab):
+        """sml_slab_create: sml_hybrid_set_slab's checks, the index tables, the members' slab
+        buffers; the atmo context's outvec rows widen to the exchange width."""
+        h = ctypes.c_void_p()
+        try:
+            with torch.cuda.device(self.dev):
+                check(lib().sml_slab_create(self.res.handle, slab.res.handle, ptr(slab.base_sst), ptr(slab.sea_mask),
+                                            int(slab.timestep), int(slab.timestep_slab), float(slab.sst_bias),
+                                            ctypes.byref(h)))
+        except SmlError as err:  # the native loop's refusals, with their reason
+            raise ValueError(f"slab: {err}") from None
+        self._slab_h = h
+        w = ctypes.c_int()
+        check(lib().sml_slab_info(h, None, ctypes.byref(w), None, None, None, None))
+        self.exchange_width = w.value
+        self.res.set_outvec_ld(w.value)  # (set by the create already: the binding's copy of it)
+        self.ov = torch.zeros((self.E, self.res.nlocal, w.value), dtype=torch.float64, device=self.dev)
+        if self.res_cus > 0:  # the slab step runs on the main stream too
+            slab.res.set_update_cus(self.res_cus)
+
+    def _strides(self):
+        return int(self.ov.stride(0)), int(self.fb.stride(0))
 
     def _cu_stream(self, first, count):
         h = ctypes.c_void_p()
@@ -94,7 +140,43 @@ class EnsembleLoop:
         return torch.cuda.ExternalStream(h.value, device=self.dev)
 
     def _tile_feedback(self, e):
+        # (the start's feedback takes the fixed tisr with a table set too, as sml_hybrid_start's)
         self.res.tile_feedback(self.g4[e], self.g2[e], self.pr[e], self.tisr, self.fb[e], stream=self.main)
+
+    def set_calendar(self, startyear: int, hours_base: int, step_hours: int = 6):
+        """run_model's calendar (HybridLoop.set_calendar): step t hands every member's window
+        the date of hour hours_base + t * step_hours and refreshes its forcing at that date
+        (Dynamics.fordate; every Dynamics needs set_surface).  Shared with the tisr table's;
+        the step count restarts."""
+        if step_hours <= 0 or hours_base < 0:
+            raise ValueError("set_calendar: step_hours > 0 and hours_base >= 0 expected")
+        self._startyear, self._base, self._step_hours = int(startyear), int(hours_base), int(step_hours)
+        self._feb29, self.t, self._cal_on = 0, 0, True
+
+    def set_tisr_table(self, table, startyear: int, hours_base: int, step_hours: int = 6):
+        """get_tisr_by_date (HybridLoop.set_tisr_table): hourly global tisr fields `table`
+        [nhours >= 8760, 48, 96] (device) shared by the members; None switches back to the
+        fixed tisr.  The step count restarts."""
+        if table is not None:
+            if step_hours <= 0 or hours_base < 0 or table.dim() != 3 or table.shape[0] < 8760 \
+                    or tuple(table.shape[1:]) != (48, 96) or not table.is_contiguous() \
+                    or table.dtype != torch.float64 or not table.is_cuda:
+                raise ValueError("set_tisr_table: a contiguous float64 device table [>= 8760, 48, 96], "
+                                 "step_hours > 0 and hours_base >= 0 expected")
+        self._table = table
+        self._startyear, self._base, self._step_hours = int(startyear), int(hours_base), int(step_hours)
+        self._feb29, self.t = 0, 0
+
+    def _date(self, t, feb29):
+        d = (ctypes.c_int * 4)()
+        check(lib().sml_calendar_delta_hour(self._startyear, self._base + t * self._step_hours, ctypes.byref(feb29), d))
+        return tuple(d)
+
+    def window_date(self):
+        """(year, month, day, hour) of the next step's windows."""
+        if not self._cal_on:
+            raise RuntimeError("no calendar (set_calendar)")
+        return self._date(self.t + 1, ctypes.c_int(self._feb29))
 
     def start(self, e, g4, g2, pr, f4, f2):
         """start_prediction analogue for member e: its analysis grid (g4, g2, pr) and a
@@ -109,6 +191,8 @@ class EnsembleLoop:
             # not discarded it already, was built from the old feedback
             self.res.cancel_step()
             self._started.clear()
+            self._slab_started.clear()
+        self._slab_started.discard(e)
         with torch.cuda.stream(self.main):
             for dst, src in ((self.g4, g4), (self.g2, g2), (self.pr, pr), (self.f4, f4), (self.f2, f2)):
                 dst[e].copy_(src)
@@ -118,20 +202,92 @@ class EnsembleLoop:
             self.res.begin_members(self.fb, stream=self.main)
         self.main.synchronize()
 
+    def start_slab(self, e, slab_outvec):
+        """start_prediction_slab's hand-over for member e, after its start: the slab
+        reservoirs' sst [nslab, 4] (device) until their first prediction (sml_slab_start;
+        their states are the host's to synchronize, slab.res.set_state(..., member=e))."""
+        if self._slab_h is None:
+            raise RuntimeError("no slab ocean in this loop (slab=)")
+        if not 0 <= e < self.E:
+            raise ValueError(f"member {e} out of range [0, {self.E})")
+        if e not in self._started:
+            raise RuntimeError(f"start_slab of member {e} before its start")
+        ovs, _ = self._strides()
+        check(lib().sml_slab_start(self._slab_h, int(e), ptr(slab_outvec), ptr(self.ov), ovs, self.main.cuda_stream))
+        self._slab_started.add(e)
+
+    def slab_state(self, e):
+        """Host copies of member e's slab state (after the loop's work completes), as
+        HybridLoop.slab_state: wholegrid_sst [48, 96], the ring [ratio - 1, tot], the last
+        slab feedback [tot] and slab outvecs [nslab, 4]."""
+        if self._slab_h is None:
+            raise RuntimeError("no slab ocean in this loop (slab=)")
+        if not 0 <= e < self.E:
+            raise ValueError(f"member {e} out of range [0, {self.E})")
+        p = [ctypes.c_void_p() for _ in range(4)]
+        st = [ctypes.c_int64() for _ in range(4)]
+        args = [x for pair in zip(p, st) for x in (ctypes.byref(pair[0]), ctypes.byref(pair[1]))]
+        check(lib().sml_slab_buffers(self._slab_h, *args))
+        cols, n = ctypes.c_int(), ctypes.c_int()
+        check(lib().sml_slab_info(self._slab_h, None, None, None, ctypes.byref(cols), ctypes.byref(n), None))
+        out = {"sst": np.zeros((48, 96)), "ring": np.zeros((cols.value, n.value)), "feedback": np.zeros(n.value),
+               "outvec": np.zeros((self.slab.res.nlocal, 4))}
+        for key, src, stride in zip(("sst", "ring", "feedback", "outvec"), p, st):
+            a = out[key]
+            if a.size:
+                check(lib().sml_copy_to_host(ptr(a), ctypes.c_void_p(src.value + 8 * e * stride.value), a.nbytes))
+        return out
+
     def step(self):
         """One hybrid time step of every member.  Returns when the E windows are done; the
         next step's begin may still run on the main stream (`sync()` waits for it)."""
         if len(self._started) != self.E:
             raise RuntimeError("EnsembleLoop.step before every member's start")
-        res = self.res
+        if self._slab_h is not None and len(self._slab_started) != self.E:
+            raise RuntimeError("EnsembleLoop.step before every member's start_slab")
+        res, L, m = self.res, lib(), self.main.cuda_stream
+        # the date of step t + 1 and the table's hour of step t, once for all members and ahead
+        # of any launch (a refusal leaves the loop as it was); the date first: the two lookups
+        # share the calendar's February latch, and run_model's comes first in the reference
+        feb29, date, field = ctypes.c_int(self._feb29), None, None
+        if self._cal_on:
+            date = self._date(self.t + 1, feb29)
+        if self._table is not None:
+            idx = ctypes.c_int()
+            check(L.sml_tisr_date_index(self._startyear, self._base + self.t * self._step_hours, ctypes.byref(feb29),
+                                        ctypes.byref(idx)))
+            if not 1 <= idx.value <= self._table.shape[0]:
+                raise ValueError(f"tisr hour {idx.value} outside the table's {self._table.shape[0]} hours")
+            field = self._table[idx.value - 1]
+        self._feb29 = feb29.value
+        ovs, fbs = self._strides()
+        if self._slab_h is not None:  # predict_slab_ml of every member, on a slab step
+            check(L.sml_slab_predict(self._slab_h, self.t + 1, ptr(self.ov), ovs, m, None))
         res.finish_assemble_members(self.f4, self.f2, self.lm if res.ncs else None, self.ov, self.g4, self.g2,
                                     self.pr, stream=self.main)
-        for e in range(self.E):
-            self._tile_feedback(e)
+        if self._slab_h is not None:  # a new SST: the grids, the feedbacks' sst entries, the windows' sst_am
+            wrote = ctypes.c_int()
+            check(L.sml_slab_sst(self._slab_h, ptr(self.ov), ovs, ptr(self.fb), fbs, m, ctypes.byref(wrote)))
+            if wrote.value:
+                sst, stride = ctypes.c_void_p(), ctypes.c_int64()
+                check(L.sml_slab_buffers(self._slab_h, ctypes.byref(sst), ctypes.byref(stride), None, None, None, None,
+                                         None, None))
+                for e, dyn in enumerate(self.dyns):
+                    check(L.sml_dyn_set_hybrid_sst(dyn._h, ctypes.c_void_p(sst.value + 8 * e * stride.value),
+                                                   float(self.slab.sst_bias), m))
+        self.t += 1
+        res.tile_feedback_members(self.g4, self.g2, self.pr, None if field is not None else self.tisr, self.fb,
+                                  stream=self.main)
+        if field is not None:  # get_tisr_by_date(..., timestep - 1, ...) for the next feedback
+            res.tile_tisr_field_members(field, self.fb, stream=self.main)
+        if self._slab_h is not None:  # averaged_atmo_input_vec(:, mod(t-1, R-1)+1)
+            check(L.sml_slab_ring(self._slab_h, self.t, ptr(self.fb), fbs, m))
         self._tiled.record(self.main)
         res.begin_members(self.fb, stream=self.main)
         self.side.wait_event(self._tiled)
         for e, dyn in enumerate(self.dyns):
+            if date is not None:  # the window's forcing at the date, behind any new SST
+                dyn.fordate(date[0], date[1], date[2], stream=self.side)
             dyn.run_model(self.g4[e], self.g2[e], self.f4[e], self.f2[e], nleap=self.nleap, delt=self.delt,
                           alph=ALPH, stream=self.side)
             # the safety rule: window e and its check are done before window e + 1 is enqueued
@@ -148,6 +304,7 @@ class EnsembleLoop:
         the last finished step computed.  The next step() needs a start() of every member."""
         self.res.cancel_step()
         self._started.clear()
+        self._slab_started.clear()
 
     def sync(self):
         self.main.synchronize()
@@ -160,6 +317,9 @@ class EnsembleLoop:
             for h in self._streams:
                 check(lib().sml_stream_destroy(h))
             self._streams = []
+        if getattr(self, "_slab_h", None):
+            check(lib().sml_slab_destroy(self._slab_h))
+            self._slab_h = None
 
     def __del__(self):
         try:

@@ -239,6 +239,22 @@ class Reservoirs:
                                                          ptr(d_outvec), ovs, ptr(g4), g4s, ptr(g2), ptr(pr), g2s,
                                                          stream_ptr(stream)))
 
+    def tile_feedback_members(self, g4, g2, pr, d_tisr, d_feedback, stream=None):
+        """tile_feedback for every member in one launch (sml_res_tile_feedback_members): g4
+        [E, 8, 48, 96, 4], g2 / pr [E, 48, 96], d_feedback [E, >= total feedback]; d_tisr
+        [nlocal, 16], the members' common one, or None (the tisr entries stay)."""
+        g4s, g2s = self._member_grids(g4, g2, ("g4", "g2", "pr"), pr=pr)
+        fbs = self._member_rows(d_feedback, "d_feedback", (self.members,), int(self.fb_offsets[-1]))
+        check(lib().sml_res_tile_feedback_members(self._h, ptr(g4), g4s, ptr(g2), ptr(pr), g2s, ptr(d_tisr),
+                                                  ptr(d_feedback), fbs, stream_ptr(stream)))
+
+    def tile_tisr_field_members(self, d_tisr_grid, d_feedback, stream=None):
+        """One hour's global tisr field [48, 96] into every member's feedback
+        (sml_res_tile_tisr_field_members)."""
+        fbs = self._member_rows(d_feedback, "d_feedback", (self.members,), int(self.fb_offsets[-1]))
+        check(lib().sml_res_tile_tisr_field_members(self._h, ptr(d_tisr_grid), ptr(d_feedback), fbs,
+                                                    stream_ptr(stream)))
+
     def member_finish_tile(self) -> int:
         """Members one block of the grid finish serves (sml_res_member_finish_tile); 1 at
         more than one member: the single-member kernel once per member."""

@@ -22,6 +22,13 @@ process, --repeats windows of --window seconds after a warm-up:
             check's time-out
 --host-only runs the host sequence alone: with SML_LIB naming another build of the library
 (the parent commit's) it is that build's side of the loop comparison on the same machine.
+--slab, --calendar and --tisr-table (any of them) add a fourth pair:
+  options : EnsembleLoop.step with the chosen options against the plain loop on the same
+            context and SPEEDY models, alternating in one process: every window restarts the
+            members, warms up and times a whole number of slab cycles (timestep_slab /
+            timestep steps: one slab step in each) by the host clock.  The slab reservoirs are
+            full size (n 4000 + the sst) unless --n-override reduces them too.
+--loop-only skips the begin, finish and host-sequence pairs.
 Prints one JSON line per E and markdown tables.  Needs the GPU; there is no CPU path.
 """
 from __future__ import annotations
@@ -48,6 +55,10 @@ def main():
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--n-override", type=int, default=None, help="reduced n (a rehearsal, not a measurement)")
     ap.add_argument("--host-only", action="store_true", help="the host sequence alone (any build of the library)")
+    ap.add_argument("--slab", action="store_true", help="the options pair: the slab ocean (1027 slab reservoirs)")
+    ap.add_argument("--calendar", action="store_true", help="the options pair: run_model's date drives fordate")
+    ap.add_argument("--tisr-table", action="store_true", help="the options pair: tisr by date from an hourly table")
+    ap.add_argument("--loop-only", action="store_true", help="skip the begin, finish and host-sequence pairs")
     ap.add_argument("--out", default=None, help="also write the JSON lines here")
     args = ap.parse_args()
 
@@ -90,12 +101,41 @@ def main():
     tisr = t(np.random.default_rng(13).standard_normal((nl, 16)))
     st0, forcing = dyn_state()
 
+    options = args.slab or args.calendar or args.tisr_table
+    if args.host_only and (options or args.loop_only):
+        sys.exit("--host-only runs the host sequence alone")
+
     def dynamics():
         d = Dynamics()
         d.set_forcing(**forcing)
         d.set_state(st0)
-        d.set_physics(phys_boundary(d, forcing["phis"]))
+        bc = phys_boundary(d, forcing["phis"])
+        if options:  # the date-driven forcing's inputs, as bench.py's loop has them
+            from speedy_ml_amd.synthetic import surface_climatology
+            surf, clim = surface_climatology(bc["fmask1"])
+            bc["fmask1"] = surf["fmask_l"]
+        d.set_physics(bc)
+        if options:
+            d.set_surface(surf)
+            d.set_climatology(clim)
         return d
+
+    slab = table = None
+    if args.slab:
+        from speedy_ml_amd.synthetic import slab_fields, slab_start_outvec, slab_weights
+
+        sreg = [r for r in regions if mask[r]]
+        sws = [slab_weights(r, n_override=args.n_override and 200) for r in sreg]
+        slab = Reservoirs(sreg, [0] * len(sreg), [w.n for w in sws], [w.k for w in sws], chunk_speedy=0, nout=4,
+                          ninp=[w.ninp for w in sws], out_index=[35] * 4, weight_dtype="f32")
+        for j, w in enumerate(sws):
+            slab.load_region_weights(j, w)
+        sx0 = [initial_state(r, w.n, seed=17) for r, w in zip(sreg, sws)]
+        del sws
+        base, smask, _, _ = slab_fields()
+        print(f"loaded {len(sreg)} slab reservoirs ({time.time() - t0:.1f}s)", flush=True)
+    if args.tisr_table:
+        table = torch.from_numpy(300.0 + 100.0 * np.random.default_rng(21).random((8760, 48, 96))).to(dev)
 
     dyns = [dynamics() for _ in range(emax)]
     hh = ctypes.c_void_p()  # the host sequence's stream: every CU, not the default stream
@@ -139,6 +179,67 @@ def main():
         torch.cuda.synchronize()
         return (time.perf_counter() - t1) * 1e3 / nsteps
 
+    def options_pair(E, rec, starts, flags, healthy):
+        """EnsembleLoop.step with the options against the plain loop, alternating."""
+        from speedy_ml_amd.ensemble import EnsembleLoop
+        from speedy_ml_amd.hybrid import SlabOcean
+
+        set_members(E)
+        cycle = 28  # timestep_slab / timestep of the reference (168 h / 6 h): one slab step a cycle
+        cal = (1981, 227520 + 24 * 40)
+        ocean = sov = None
+        if slab is not None:
+            slab.set_members(E)
+            sov = t(np.stack([slab_start_outvec(r) for r in sreg]))
+            ocean = SlabOcean(slab, t(base), t(smask))  # timestep 6 h, timestep_slab 168 h
+        variants = {"plain": EnsembleLoop(res, dyns[:E], dev, tisr=tisr),
+                    "options": EnsembleLoop(res, dyns[:E], dev, tisr=tisr, slab=ocean)}
+        full = variants["options"]
+        widths = {"plain": res.nout, "options": full.exchange_width}
+
+        def restart(name):
+            loop = variants[name]
+            if res.step_begun():
+                res.cancel_step()
+            res.set_outvec_ld(widths[name])  # the two loops' outvec rows differ by the slab's sst columns
+            if name == "options":
+                if args.tisr_table:
+                    loop.set_tisr_table(table, *cal)
+                if args.calendar:
+                    loop.set_calendar(*cal)
+            for e in range(E):
+                loop.start(e, *starts[e])
+                if name == "options" and slab is not None:
+                    for j in range(len(sreg)):
+                        slab.set_state(j, sx0[j] * (1.0 - 0.01 * e), member=e)
+                    loop.start_slab(e, sov)
+            return loop
+
+        for name in variants:  # warm every shape, the slab step included
+            loop = restart(name)
+            ms = host_clock(loop.step, loop.sync, 1)
+            flags[:] = loop.run_speedy()
+            healthy(f"EnsembleLoop.step ({name}), first step", ms)
+            ms = host_clock(loop.step, loop.sync, cycle)
+        ncyc = max(1, min(8, int(np.ceil(args.window * 1e3 / (ms * cycle)))))
+        rec["options"] = dict(slab=args.slab, calendar=args.calendar, tisr_table=args.tisr_table,
+                              steps_per_window=ncyc * cycle)
+        rec["plain_ms"], rec["options_ms"] = [], []
+        for _ in range(args.repeats):
+            for name in variants:
+                loop = restart(name)
+                host_clock(loop.step, loop.sync, 3)  # (every timed cycle holds one slab step, whatever its phase)
+                rec[name + "_ms"].append(round(host_clock(loop.step, loop.sync, ncyc * cycle), 4))
+                flags[:] = loop.run_speedy()
+                healthy(f"EnsembleLoop.step ({name}) window", rec[name + "_ms"][-1])
+        for loop in variants.values():
+            loop.sync()
+        if res.step_begun():
+            res.cancel_step()
+        for loop in variants.values():
+            loop.close()
+        res.set_outvec_ld(res.nout)
+
     nop = lambda: None  # noqa: E731
     lines = []
     for E in args.members:
@@ -159,7 +260,7 @@ def main():
             f4[e].copy_(starts[e][3])
             f2[e].copy_(starts[e][4])
 
-        if not args.host_only:
+        if not args.host_only and not args.loop_only:
             # ---- begin_members against predict_members
             begin = lambda: res.begin_members(fb)  # noqa: E731
             finish = lambda: res.finish_members(lm, ov)  # noqa: E731
@@ -224,15 +325,16 @@ def main():
 
         for d in dyns[:E]:
             d.set_state(st0)
-        host_start()
-        healthy("host sequence, first step", host_clock(host_step, hstream.synchronize, 1))
-        host_clock(host_step, hstream.synchronize, 5)
-        ms = host_clock(host_step, hstream.synchronize, 5)
-        healthy("host sequence", ms)
-        nsteps = max(10, min(400, int(np.ceil(args.window * 1e3 / ms))))
         rec["host_sequence_ms"], rec["loop_step_ms"] = [], []
         loop = None
-        if not args.host_only:
+        if not args.loop_only:
+            host_start()
+            healthy("host sequence, first step", host_clock(host_step, hstream.synchronize, 1))
+            host_clock(host_step, hstream.synchronize, 5)
+            ms = host_clock(host_step, hstream.synchronize, 5)
+            healthy("host sequence", ms)
+            nsteps = max(10, min(400, int(np.ceil(args.window * 1e3 / ms))))
+        if not args.host_only and not args.loop_only:
             from speedy_ml_amd.ensemble import EnsembleLoop
 
             set_members(E)
@@ -243,7 +345,7 @@ def main():
             flags[:] = loop.run_speedy()
             healthy("EnsembleLoop.step, first step", ms)
             host_clock(loop.step, loop.sync, 10)
-        for _ in range(args.repeats):
+        for _ in range(0 if args.loop_only else args.repeats):
             if loop is not None:
                 rec["loop_step_ms"].append(round(host_clock(loop.step, loop.sync, nsteps), 4))
                 flags[:] = loop.run_speedy()
@@ -260,12 +362,14 @@ def main():
             loop.sync()
             res.cancel_step()
             loop.close()
+        if options:
+            options_pair(E, rec, starts, flags, healthy)
         lines.append(rec)
         print(json.dumps(rec), flush=True)
 
     med = lambda v: float(np.median(v))  # noqa: E731
     spread = lambda v: float(max(v) - min(v))  # noqa: E731
-    if not args.host_only:
+    if not args.host_only and not args.loop_only:
         print("\n| E | begin_members ms | spread | predict_members ms | spread |")
         print("|---|---|---|---|---|")
         for r in lines:
@@ -276,12 +380,21 @@ def main():
         for r in lines:
             cells = ", ".join(f"TF {tf}: {med(v):.4f} ({spread(v):.4f})" for tf, v in r["finish_ms"].items())
             print(f"| {r['E']} | {cells} |")
-    print("\n| E | EnsembleLoop.step ms | spread | host sequence ms | spread | library |")
-    print("|---|---|---|---|---|---|")
-    for r in lines:
-        ls = r["loop_step_ms"]
-        print(f"| {r['E']} | " + (f"{med(ls):.3f} | {spread(ls):.3f}" if ls else "- | -") +
-              f" | {med(r['host_sequence_ms']):.3f} | {spread(r['host_sequence_ms']):.3f} | {r['lib']} |")
+    if not args.loop_only:
+        print("\n| E | EnsembleLoop.step ms | spread | host sequence ms | spread | library |")
+        print("|---|---|---|---|---|---|")
+        for r in lines:
+            ls = r["loop_step_ms"]
+            print(f"| {r['E']} | " + (f"{med(ls):.3f} | {spread(ls):.3f}" if ls else "- | -") +
+                  f" | {med(r['host_sequence_ms']):.3f} | {spread(r['host_sequence_ms']):.3f} | {r['lib']} |")
+    if options:
+        on = ", ".join(k for k in ("slab", "calendar", "tisr_table") if getattr(args, k))
+        print(f"\n| E | plain EnsembleLoop.step ms | spread | with {on} ms | spread | difference ms |")
+        print("|---|---|---|---|---|---|")
+        for r in lines:
+            a, b = r["plain_ms"], r["options_ms"]
+            print(f"| {r['E']} | {med(a):.3f} | {spread(a):.3f} | {med(b):.3f} | {spread(b):.3f} | "
+                  f"{med(b) - med(a):+.3f} |")
     hstream.synchronize()
     check(lib().sml_stream_destroy(hh))
     if args.out:
