@@ -865,6 +865,47 @@ int sml_slab_ring(sml_slab *s, int64_t t, const double *d_feedback, int64_t fb_s
 int sml_slab_buffers(const sml_slab *s, const double **d_sst_grid, int64_t *sst_stride, const double **d_ring,
                      int64_t *ring_stride, const double **d_slab_feedback, int64_t *fb_stride,
                      const double **d_slab_outvec, int64_t *ov_stride);
+/* ---- the products of an E-member forecast: per-point mean and spread of the members'
+ * assembled grids, and per step a row of area-weighted scores against a verifying analysis.
+ * Fields: f = 4k + v is level k, variable v of a grid4d [8][48][96][4]; 32 is logp
+ * [48][96], 33 precip [48][96].  Member e of d_g4 starts e * g4_stride doubles in, of d_g2
+ * and d_pr e * g2_stride (>= the packed grids, else SML_ERR_ARG naming the stride).  d_pr
+ * may be NULL: field 33 is then left untouched everywhere.  Per point, in member order:
+ *   mean = (x_0 + x_1 + ...) / E;  var = sum_e (x_e - mean)^2 / (E - 1);  spread = sqrt(var)
+ * (spread 0 at E = 1).  Point (j, i) weighs w_j = wt[min(j, 47 - j)] / (96 * sum_j wt[..]),
+ * wt the Gaussian weights of sml_spectral_tables (sml_ens_weights; the 4608 weights sum to
+ * 1).  Row t of scores [capacity][34][4] holds, summed over the field's points,
+ *   rmse = sqrt(sum w (mean - y)^2), spread = sqrt(sum w var), bias = sum w (mean - y),
+ *   crps = sum w [ 1/E sum_e |x_e - y| - 1/(2E(E-1)) sum_e sum_f |x_e - x_f| ]  (the fair CRPS)
+ * and row t of ranks [capacity][34][33] counts the points by r = #{e : x_e < y} (ties and
+ * NaN count as not below; bins above E stay 0).  The truth is three single-member grids:
+ * all NULL (only `spread` of the row is written), or d_truth4 and d_truth2 with d_truthpr
+ * or without (field 33 then as without truth).  The sums use no atomics and a fixed order:
+ * for given inputs the tables are bit for bit the same across calls, streams, CU masks
+ * and strides.  Launches are stream-ordered with no host synchronisation; the calls on one
+ * context must be ordered among themselves. */
+typedef struct sml_ens sml_ens;
+/* members in 1..SML_RES_MAX_MEMBERS, capacity_steps >= 1 rows; the tables start reset */
+int sml_ens_create(int members, int capacity_steps, sml_ens **out);
+int sml_ens_destroy(sml_ens *e);
+/* members, capacity, 34 fields, 4 scores per field, 33 rank bins; any may be NULL */
+int sml_ens_info(const sml_ens *e, int *members, int *capacity_steps, int *fields, int *scores_per_field,
+                 int *rank_bins);
+/* quiet NaN into every score, 0 into every rank bin */
+int sml_ens_reset(sml_ens *e, void *stream);
+/* mean and spread in the packed single-member layouts; any output may be NULL */
+int sml_ens_moments(sml_ens *e, const double *d_g4, int64_t g4_stride, const double *d_g2, const double *d_pr,
+                    int64_t g2_stride, double *d_mean4, double *d_mean2, double *d_meanpr, double *d_spread4,
+                    double *d_spread2, double *d_spreadpr, void *stream);
+/* row t in [0, capacity) of both tables, else SML_ERR_ARG */
+int sml_ens_scores(sml_ens *e, const double *d_g4, int64_t g4_stride, const double *d_g2, const double *d_pr,
+                   int64_t g2_stride, const double *d_truth4, const double *d_truth2, const double *d_truthpr, int t,
+                   void *stream);
+/* rows [t0, t0 + count) to the host: scores [count][34][4], ranks [count][34][33] (either
+ * may be NULL).  Waits for the device. */
+int sml_ens_read(sml_ens *e, int t0, int count, double *scores, int32_t *ranks);
+/* the 48 row weights w_j (host only, no context) */
+int sml_ens_weights(double *w48);
 /* the two cross-stream dependencies of the overlapped loop: SML_HOP_WAIT_VALUE (a
  * sequence number written by the producer's stream, waited for by the consumer's, as
  * CP stream memory operations), SML_HOP_EVENTS (event record + wait), SML_HOP_KERNEL

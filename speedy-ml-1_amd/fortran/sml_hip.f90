@@ -657,6 +657,58 @@ module sml_hip
       integer(c_int64_t), intent(out) :: sst_stride, ring_stride, fb_stride, ov_stride
       integer(c_int) :: rc
     end function
+    !> the products of an E-member forecast: per-point mean and spread, and per step a row
+    !> of area-weighted scores and rank histograms (include/speedy_ml.h, sml_ens_*)
+    function sml_ens_create(members, capacity_steps, e) bind(C, name='sml_ens_create') result(rc)
+      import :: c_ptr, c_int
+      integer(c_int), value :: members, capacity_steps
+      type(c_ptr), intent(out) :: e
+      integer(c_int) :: rc
+    end function
+    function sml_ens_destroy(e) bind(C, name='sml_ens_destroy') result(rc)
+      import :: c_ptr, c_int
+      type(c_ptr), value :: e
+      integer(c_int) :: rc
+    end function
+    function sml_ens_info(e, members, capacity_steps, fields, scores_per_field, rank_bins) &
+        bind(C, name='sml_ens_info') result(rc)
+      import :: c_ptr, c_int
+      type(c_ptr), value :: e
+      integer(c_int), intent(out) :: members, capacity_steps, fields, scores_per_field, rank_bins
+      integer(c_int) :: rc
+    end function
+    function sml_ens_reset(e, stream) bind(C, name='sml_ens_reset') result(rc)
+      import :: c_ptr, c_int
+      type(c_ptr), value :: e, stream
+      integer(c_int) :: rc
+    end function
+    function sml_ens_moments(e, d_g4, g4_stride, d_g2, d_pr, g2_stride, d_mean4, d_mean2, d_meanpr, &
+        d_spread4, d_spread2, d_spreadpr, stream) bind(C, name='sml_ens_moments') result(rc)
+      import :: c_ptr, c_int, c_int64_t
+      type(c_ptr), value :: e, d_g4, d_g2, d_pr, d_mean4, d_mean2, d_meanpr, d_spread4, d_spread2, d_spreadpr, stream
+      integer(c_int64_t), value :: g4_stride, g2_stride
+      integer(c_int) :: rc
+    end function
+    function sml_ens_scores(e, d_g4, g4_stride, d_g2, d_pr, g2_stride, d_truth4, d_truth2, d_truthpr, t, stream) &
+        bind(C, name='sml_ens_scores') result(rc)
+      import :: c_ptr, c_int, c_int64_t
+      type(c_ptr), value :: e, d_g4, d_g2, d_pr, d_truth4, d_truth2, d_truthpr, stream
+      integer(c_int64_t), value :: g4_stride, g2_stride
+      integer(c_int), value :: t
+      integer(c_int) :: rc
+    end function
+    !> scores(4, 34, count), ranks(33, 34, count) on the host; waits for the device
+    function sml_ens_read(e, t0, count, scores, ranks) bind(C, name='sml_ens_read') result(rc)
+      import :: c_ptr, c_int
+      type(c_ptr), value :: e, scores, ranks
+      integer(c_int), value :: t0, count
+      integer(c_int) :: rc
+    end function
+    function sml_ens_weights(w48) bind(C, name='sml_ens_weights') result(rc)
+      import :: c_int, c_double
+      real(c_double), intent(out) :: w48(48)
+      integer(c_int) :: rc
+    end function
     !> advance from the host's all-gather output d_recv(nout, maxc, world)
     function sml_hybrid_advance_slabs(h, d_recv) bind(C, name='sml_hybrid_advance_slabs') result(rc)
       import :: c_ptr, c_int

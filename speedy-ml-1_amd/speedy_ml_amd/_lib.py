@@ -72,6 +72,8 @@ EXPORTED = (
     "sml_res_tile_feedback_members", "sml_res_tile_tisr_field_members",
     "sml_slab_create", "sml_slab_destroy", "sml_slab_info", "sml_slab_start", "sml_slab_predict", "sml_slab_sst",
     "sml_slab_ring", "sml_slab_buffers",
+    "sml_ens_create", "sml_ens_destroy", "sml_ens_info", "sml_ens_reset", "sml_ens_moments", "sml_ens_scores",
+    "sml_ens_read", "sml_ens_weights",
 )
 
 SML_HOP_AUTO, SML_HOP_WAIT_VALUE, SML_HOP_EVENTS, SML_HOP_KERNEL = 0, 1, 2, 3
@@ -303,6 +305,14 @@ def _declare(L: ctypes.CDLL) -> None:
         "sml_slab_sst": [vp, vp, i64, vp, i64, vp, ip],
         "sml_slab_ring": [vp, i64, vp, i64, vp],
         "sml_slab_buffers": [vp, pp, i64p, pp, i64p, pp, i64p, pp, i64p],
+        "sml_ens_create": [i, i, pp],
+        "sml_ens_destroy": [vp],
+        "sml_ens_info": [vp, ip, ip, ip, ip, ip],
+        "sml_ens_reset": [vp, vp],
+        "sml_ens_moments": [vp, vp, i64, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp],
+        "sml_ens_scores": [vp, vp, i64, vp, vp, i64, vp, vp, vp, i, vp],
+        "sml_ens_read": [vp, i, i, vp, vp],
+        "sml_ens_weights": [vp],
     }
     for name, args in sig.items():
         if os.environ.get("SML_LIB") and not hasattr(L, name):

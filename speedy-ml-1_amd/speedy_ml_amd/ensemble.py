@@ -22,6 +22,9 @@ that every member is that loop:
                the slab ring's column (sml_slab_ring): one launch each        -> event
                begin_members(fb): the next step's update and v_ml (the states run one update
                ahead, as the pipelined HybridLoop's do; cancel_step() rolls them back)
+               with set_products: the ensemble mean and spread of g4, g2, pr and the step's
+               row of scores (sml_ens_moments, sml_ens_scores) behind the begin -- the grids
+               are complete by then and stay as they are until the next step's finish
   side stream  waits for the event, then for e = 0 .. E - 1: dyns[e].fordate(date) with the
                calendar on, dyns[e].run_model(g4[e], g2[e] -> f4[e], f2[e]); the host waits
                for window e (its safety flag, then the stream) before it enqueues window e + 1.
@@ -29,6 +32,8 @@ That host wait is a safety rule, not a convenience: every Dynamics has a check s
 kernel polls in-kernel, an in-kernel wait holds its hardware queue, and
 the E contexts' streams share the process's few queues -- so no window is enqueued while
 another context's window or check is outstanding.
+
+EnsembleProducts is that reduction over the members on its own.
 
 The slab ocean (`slab=`), run_model's calendar (set_calendar) and get_tisr_by_date
 (set_tisr_table) are HybridLoop's, with the same refusals.
@@ -46,6 +51,103 @@ import torch
 
 from ._lib import SmlError, check, lib, ptr
 from .dynamics import ALPH, DELT
+
+
+def _member_stride(a, shape, what):
+    """The member stride in doubles of a members' device array [E, *shape] whose members
+    are packed."""
+    if a.dtype != torch.float64 or not a.is_cuda or tuple(a.shape[1:]) != shape or not a[0].is_contiguous():
+        raise ValueError(f"{what}: a float64 device tensor [E, {', '.join(map(str, shape))}] with packed members expected")
+    return int(a.stride(0)) if a.shape[0] > 1 else int(np.prod(shape))
+
+
+class EnsembleProducts:
+    """What an E-member forecast is run for (sml_ens_*, include/speedy_ml.h): the per-point
+    ensemble mean and spread of the members' grids g4 [E, 8, 48, 96, 4], g2 [E, 48, 96],
+    pr [E, 48, 96] or None, and per step a row of area-weighted scores of each of the 34
+    fields (4 k + v: level k, variable v; 32 logp; 33 precip) against a verifying analysis:
+    scores [capacity, 34, 4] = rmse of the mean, spread, fair CRPS, bias, and the rank
+    histogram ranks [capacity, 34, 33].  The tables live on the device; read() copies rows
+    to the host.  Calls on one object are to be made in stream order."""
+
+    RMSE, SPREAD, CRPS, BIAS = 0, 1, 2, 3
+
+    def __init__(self, members: int, capacity: int, device):
+        self.dev = torch.device(device)
+        self._h = None
+        h = ctypes.c_void_p()
+        with torch.cuda.device(self.dev):
+            check(lib().sml_ens_create(int(members), int(capacity), ctypes.byref(h)))
+        self._h = h
+        self.members, self.capacity = int(members), int(capacity)
+        n = [ctypes.c_int() for _ in range(3)]
+        check(lib().sml_ens_info(h, None, None, *[ctypes.byref(x) for x in n]))
+        self.fields, self.nscores, self.rank_bins = (x.value for x in n)
+
+    def _inputs(self, g4, g2, pr):
+        if g4.shape[0] != self.members or g2.shape[0] != self.members or (pr is not None and pr.shape[0] != self.members):
+            raise ValueError(f"{self.members} members expected")
+        s4, s2 = _member_stride(g4, (8, 48, 96, 4), "g4"), _member_stride(g2, (48, 96), "g2")
+        if pr is not None and _member_stride(pr, (48, 96), "pr") != s2:
+            raise ValueError("pr: the member stride of g2 expected")
+        return ptr(g4), s4, ptr(g2), ptr(pr), s2
+
+    def moments(self, g4, g2, pr=None, mean=True, spread=True, out=None, stream=None):
+        """(mean4, mean2, meanpr, spread4, spread2, spreadpr) in the single-member layouts;
+        None where not asked for (mean / spread off, pr None).  `out`: such a tuple of
+        tensors to write into instead of new ones."""
+        a = self._inputs(g4, g2, pr)
+        if out is None:
+            z = lambda on, *s: torch.empty(s, dtype=torch.float64, device=self.dev) if on else None  # noqa: E731
+            out = (z(mean, 8, 48, 96, 4), z(mean, 48, 96), z(mean and pr is not None, 48, 96),
+                   z(spread, 8, 48, 96, 4), z(spread, 48, 96), z(spread and pr is not None, 48, 96))
+        s = stream if stream is not None else torch.cuda.current_stream(self.dev)
+        check(lib().sml_ens_moments(self._h, *a, *[ptr(o) for o in out], ctypes.c_void_p(s.cuda_stream)))
+        return out
+
+    def scores(self, g4, g2, pr, truth, t: int, stream=None):
+        """Row t of the tables.  truth: None (only the row's spread is written), or
+        (truth4 [8, 48, 96, 4], truth2 [48, 96], truthpr [48, 96] or None)."""
+        a = self._inputs(g4, g2, pr)
+        t4, t2, tp = truth if truth is not None else (None, None, None)
+        for x, shape in ((t4, (8, 48, 96, 4)), (t2, (48, 96)), (tp, (48, 96))):
+            if x is not None and (x.dtype != torch.float64 or not x.is_cuda or tuple(x.shape) != shape
+                                  or not x.is_contiguous()):
+                raise ValueError(f"truth: contiguous float64 device tensors expected, one of them {shape}")
+        s = stream if stream is not None else torch.cuda.current_stream(self.dev)
+        check(lib().sml_ens_scores(self._h, *a, ptr(t4), ptr(t2), ptr(tp), int(t), ctypes.c_void_p(s.cuda_stream)))
+
+    def reset(self, stream=None):
+        """Quiet NaN into every score, 0 into every rank bin."""
+        s = stream if stream is not None else torch.cuda.current_stream(self.dev)
+        check(lib().sml_ens_reset(self._h, ctypes.c_void_p(s.cuda_stream)))
+
+    def read(self, t0: int = 0, count: int | None = None):
+        """Host rows (scores [count, 34, 4], ranks [count, 34, 33]); waits for the device."""
+        if count is None:
+            count = self.capacity - t0
+        sc = np.empty((max(count, 0), self.fields, self.nscores))
+        rk = np.empty((max(count, 0), self.fields, self.rank_bins), dtype=np.int32)
+        check(lib().sml_ens_read(self._h, int(t0), int(count), ptr(sc), ptr(rk)))
+        return sc, rk
+
+    @staticmethod
+    def weights():
+        """The weight of one point of each of the 48 rows; 96 * sum = 1."""
+        w = np.empty(48)
+        check(lib().sml_ens_weights(ptr(w)))
+        return w
+
+    def close(self):
+        if getattr(self, "_h", None):
+            check(lib().sml_ens_destroy(self._h))
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class EnsembleLoop:
@@ -107,6 +209,8 @@ class EnsembleLoop:
         self._cal_on, self._table = False, None
         self._startyear, self._base, self._step_hours, self._feb29 = 0, 0, 6, 0
         self.exchange_width = res.nout
+        self._prod, self._prod_t, self._truth, self._prod_fields = None, 0, None, False
+        self.mean4 = self.mean2 = self.meanpr = self.spread4 = self.spread2 = self.spreadpr = None
         if slab is not None:
             self._set_slab(slab)
 
@@ -166,6 +270,62 @@ class EnsembleLoop:
         self._table = table
         self._startyear, self._base, self._step_hours = int(startyear), int(hours_base), int(step_hours)
         self._feb29, self.t = 0, 0
+
+    def set_products(self, capacity, truth=None, fields=True):
+        """Ensemble products of every step from here on (EnsembleProducts): step s = 0, 1, ..
+        after this call fills row s of the score tables from the assembled hybrid grids
+        g4, g2, pr, verified against truth[s] -- truth: None (only the spread is scored), or
+        device tensors ([T, 8, 48, 96, 4], [T, 48, 96], [T, 48, 96] or None) with
+        T >= capacity -- and, with `fields`, leaves their mean and spread in mean4 / mean2 /
+        meanpr and spread4 / spread2 / spreadpr.  The launches follow begin_members on the
+        main stream, off the chain between the finish and the windows; no loop buffer
+        changes.  A step past `capacity` refuses before anything is enqueued.
+        capacity None switches the products off: step() is then the loop without them."""
+        if capacity is not None:
+            if int(capacity) < 1:
+                raise ValueError("set_products: capacity >= 1 expected")
+            if truth is not None:
+                t4, t2, tp = truth
+                for x, shape, optional in ((t4, (8, 48, 96, 4), False), (t2, (48, 96), False), (tp, (48, 96), True)):
+                    if x is None and optional:
+                        continue
+                    if x is None or x.dtype != torch.float64 or not x.is_cuda or not x.is_contiguous() \
+                            or tuple(x.shape[1:]) != shape or x.shape[0] < int(capacity):
+                        raise ValueError(f"set_products: truth [T >= {int(capacity)}, {', '.join(map(str, shape))}], "
+                                         "contiguous float64 device tensors, expected")
+        self.sync()
+        if self._prod is not None:
+            self._prod.close()
+        self._prod, self._prod_t, self._truth, self._prod_fields = None, 0, None, False
+        self.mean4 = self.mean2 = self.meanpr = self.spread4 = self.spread2 = self.spreadpr = None
+        if capacity is None:
+            return
+        self._prod = EnsembleProducts(self.E, int(capacity), self.dev)
+        self._truth, self._prod_fields = truth, bool(fields)
+        if fields:
+            z = lambda *s: torch.zeros(s, dtype=torch.float64, device=self.dev)  # noqa: E731
+            self.mean4, self.mean2, self.meanpr = z(8, 48, 96, 4), z(48, 96), z(48, 96)
+            self.spread4, self.spread2, self.spreadpr = z(8, 48, 96, 4), z(48, 96), z(48, 96)
+
+    def products(self, t0=0, count=None):
+        """Host rows [t0, t0 + count) of the score tables (count None: up to the last step
+        done): scores [count, 34, 4] = rmse, spread, crps, bias and ranks [count, 34, 33].
+        Waits for the device."""
+        if self._prod is None:
+            raise RuntimeError("no products in this loop (set_products)")
+        return self._prod.read(t0, self._prod_t - t0 if count is None else count)
+
+    def _enqueue_products(self):
+        p, s = self._prod, self._prod_t
+        if self._prod_fields:
+            p.moments(self.g4, self.g2, self.pr, out=(self.mean4, self.mean2, self.meanpr, self.spread4, self.spread2,
+                                                      self.spreadpr), stream=self.main)
+        truth = None
+        if self._truth is not None:
+            t4, t2, tp = self._truth
+            truth = (t4[s], t2[s], tp[s] if tp is not None else None)
+        p.scores(self.g4, self.g2, self.pr, truth, s, stream=self.main)
+        self._prod_t = s + 1
 
     def _date(self, t, feb29):
         d = (ctypes.c_int * 4)()
@@ -245,6 +405,9 @@ class EnsembleLoop:
             raise RuntimeError("EnsembleLoop.step before every member's start")
         if self._slab_h is not None and len(self._slab_started) != self.E:
             raise RuntimeError("EnsembleLoop.step before every member's start_slab")
+        if self._prod is not None and self._prod_t >= self._prod.capacity:
+            raise RuntimeError(f"EnsembleLoop.step: the products' {self._prod.capacity} rows are full "
+                               "(set_products with a larger capacity, or None)")
         res, L, m = self.res, lib(), self.main.cuda_stream
         # the date of step t + 1 and the table's hour of step t, once for all members and ahead
         # of any launch (a refusal leaves the loop as it was); the date first: the two lookups
@@ -284,6 +447,8 @@ class EnsembleLoop:
             check(L.sml_slab_ring(self._slab_h, self.t, ptr(self.fb), fbs, m))
         self._tiled.record(self.main)
         res.begin_members(self.fb, stream=self.main)
+        if self._prod is not None:  # behind the begin: g4, g2, pr stay as they are until the next finish
+            self._enqueue_products()
         self.side.wait_event(self._tiled)
         for e, dyn in enumerate(self.dyns):
             if date is not None:  # the window's forcing at the date, behind any new SST
@@ -320,6 +485,9 @@ class EnsembleLoop:
         if getattr(self, "_slab_h", None):
             check(lib().sml_slab_destroy(self._slab_h))
             self._slab_h = None
+        if getattr(self, "_prod", None) is not None:
+            self._prod.close()
+            self._prod = None
 
     def __del__(self):
         try:

@@ -28,6 +28,13 @@ process, --repeats windows of --window seconds after a warm-up:
             members, warms up and times a whole number of slab cycles (timestep_slab /
             timestep steps: one slab step in each) by the host clock.  The slab reservoirs are
             full size (n 4000 + the sst) unless --n-override reduces them too.
+--products adds a pair of its own:
+  products: EnsembleLoop.step with set_products(capacity, truth) against the same loop with
+            products off, alternating in one process by the host clock, and the products' own
+            launches (sml_ens_moments + sml_ens_scores on the loop's grids) between a pair of
+            device events.  With SML_LIB naming a build without the sml_ens_* entry points (the
+            parent commit's) only the loop with products off is timed: that build's side of
+            the "off against the parent" comparison.
 --loop-only skips the begin, finish and host-sequence pairs.
 Prints one JSON line per E and markdown tables.  Needs the GPU; there is no CPU path.
 """
@@ -58,6 +65,7 @@ def main():
     ap.add_argument("--slab", action="store_true", help="the options pair: the slab ocean (1027 slab reservoirs)")
     ap.add_argument("--calendar", action="store_true", help="the options pair: run_model's date drives fordate")
     ap.add_argument("--tisr-table", action="store_true", help="the options pair: tisr by date from an hourly table")
+    ap.add_argument("--products", action="store_true", help="the products pair: set_products on against off")
     ap.add_argument("--loop-only", action="store_true", help="skip the begin, finish and host-sequence pairs")
     ap.add_argument("--out", default=None, help="also write the JSON lines here")
     args = ap.parse_args()
@@ -102,7 +110,7 @@ def main():
     st0, forcing = dyn_state()
 
     options = args.slab or args.calendar or args.tisr_table
-    if args.host_only and (options or args.loop_only):
+    if args.host_only and (options or args.loop_only or args.products):
         sys.exit("--host-only runs the host sequence alone")
 
     def dynamics():
@@ -240,6 +248,70 @@ def main():
             loop.close()
         res.set_outvec_ld(res.nout)
 
+    def products_pair(E, rec, starts, flags, healthy):
+        """EnsembleLoop.step with the ensemble products on against off, alternating; then the
+        products' own launches between device events."""
+        from speedy_ml_amd.ensemble import EnsembleLoop
+
+        have = hasattr(lib(), "sml_ens_create")
+        set_members(E)
+        for d in dyns[:E]:
+            d.set_state(st0)
+        loop = EnsembleLoop(res, dyns[:E], dev, tisr=tisr)
+        for e in range(E):
+            loop.start(e, *starts[e])
+        ms = host_clock(loop.step, loop.sync, 1)
+        flags[:] = loop.run_speedy()
+        healthy("EnsembleLoop.step (products pair), first step", ms)
+        host_clock(loop.step, loop.sync, 10)
+        ms = host_clock(loop.step, loop.sync, 10)
+        nsteps = max(10, min(400, int(np.ceil(args.window * 1e3 / ms))))
+        rec["products_steps_per_window"] = nsteps
+        rec["products_off_ms"], rec["products_on_ms"] = [], []
+        truth = None
+        if have:
+            g = torch.Generator(device="cpu").manual_seed(7)
+            truth = tuple(torch.randn((nsteps + 3,) + s, dtype=torch.float64, generator=g).to(dev)
+                          for s in ((8, 48, 96, 4), (48, 96), (48, 96)))
+        for _ in range(args.repeats):
+            if have:
+                loop.set_products(None)
+            rec["products_off_ms"].append(round(host_clock(loop.step, loop.sync, nsteps), 4))
+            flags[:] = loop.run_speedy()
+            healthy("EnsembleLoop.step, products off, window", rec["products_off_ms"][-1])
+            if have:
+                loop.set_products(nsteps + 3, truth)
+                host_clock(loop.step, loop.sync, 3)
+                rec["products_on_ms"].append(round(host_clock(loop.step, loop.sync, nsteps), 4))
+                flags[:] = loop.run_speedy()
+                healthy("EnsembleLoop.step, products on, window", rec["products_on_ms"][-1])
+        if have:
+            from speedy_ml_amd.ensemble import EnsembleProducts
+
+            loop.set_products(None)
+            loop.sync()
+            prod = EnsembleProducts(E, 1, dev)
+            out = tuple(torch.zeros(s, dtype=torch.float64, device=dev)
+                        for s in ((8, 48, 96, 4), (48, 96), (48, 96)) * 2)
+            tr0 = tuple(a[0] for a in truth)
+
+            def launches():
+                prod.moments(loop.g4, loop.g2, loop.pr, out=out, stream=hstream)
+                prod.scores(loop.g4, loop.g2, loop.pr, tr0, 0, stream=hstream)
+
+            with torch.cuda.stream(hstream):
+                n = calls_for(nop, launches, nop)
+                rec["products_launch_ms"] = [round(paired(nop, launches, nop, n), 5) for _ in range(args.repeats)]
+            grid = (147456 + 2 * 4608) * 8
+            # each kernel reads the E members once from memory (the moments' second pass and the
+            # scores' pair term re-read what the thread has just loaded); means, spreads, truth
+            rec["products_bytes"] = 2 * E * grid + 3 * grid
+            prod.close()
+        loop.sync()
+        if res.step_begun():
+            res.cancel_step()
+        loop.close()
+
     nop = lambda: None  # noqa: E731
     lines = []
     for E in args.members:
@@ -364,6 +436,8 @@ def main():
             loop.close()
         if options:
             options_pair(E, rec, starts, flags, healthy)
+        if args.products:
+            products_pair(E, rec, starts, flags, healthy)
         lines.append(rec)
         print(json.dumps(rec), flush=True)
 
@@ -395,6 +469,17 @@ def main():
             a, b = r["plain_ms"], r["options_ms"]
             print(f"| {r['E']} | {med(a):.3f} | {spread(a):.3f} | {med(b):.3f} | {spread(b):.3f} | "
                   f"{med(b) - med(a):+.3f} |")
+    if args.products:
+        print("\n| E | products off ms | spread | products on ms | spread | difference ms | own launches ms | bytes / 8 TB/s ms | library |")
+        print("|---|---|---|---|---|---|---|---|---|")
+        for r in lines:
+            a, b = r["products_off_ms"], r["products_on_ms"]
+            if b:
+                own = r["products_launch_ms"]
+                print(f"| {r['E']} | {med(a):.3f} | {spread(a):.3f} | {med(b):.3f} | {spread(b):.3f} | "
+                      f"{med(b) - med(a):+.3f} | {med(own):.4f} | {r['products_bytes'] / 8e9:.4f} | {r['lib']} |")
+            else:
+                print(f"| {r['E']} | {med(a):.3f} | {spread(a):.3f} | - | - | - | - | - | {r['lib']} |")
     hstream.synchronize()
     check(lib().sml_stream_destroy(hh))
     if args.out:
