@@ -34,6 +34,20 @@ int dyn_set_check_timeout(sml_dynamics *d, long long timeout);
 int dyn_run_model_exit_store(sml_dynamics *d, uint64_t *flag, uint64_t value);
 int dyn_run_model_entry_signal(sml_dynamics *d, uint64_t *counter, int *adds);
 int dyn_check_event(sml_dynamics *d, void **ev);  // a hipEvent_t
+// sml_slab.hip's context behind its C ABI, for the native loop: no argument or stride
+// checks, no per-call allocation.  slab_create takes the atmo context as it is (one
+// rank's share) and leaves its outvec_ld alone; slab_sst reads every region's exchange
+// rows (global region order, all_stride a member) and writes the local feedbacks;
+// slab_predict writes the local rows.  slab_strides: the packed member strides of the
+// local rows, of every region's rows and of the feedback.
+int slab_create(sml_reservoirs *atmo, sml_reservoirs *slab, const double *d_base_sst, const double *d_sea_mask,
+                int timestep, int timestep_slab, double sst_bias, sml_slab **out);
+int slab_start(sml_slab *s, int member, const double *d_slab_outvec, double *d_outvec, int64_t ov_stride, void *stream);
+int slab_predict(sml_slab *s, int64_t t_next, double *d_outvec, int64_t ov_stride, void *stream, int *predicted);
+int slab_sst(sml_slab *s, const double *d_outvec_all, int64_t all_stride, double *d_feedback, int64_t fb_stride,
+             void *stream, int *wrote);
+int slab_ring(sml_slab *s, int64_t t, const double *d_feedback, int64_t fb_stride, void *stream);
+void slab_strides(const sml_slab *s, int64_t *ov_stride, int64_t *all_stride, int64_t *fb_stride);
 
 // --------------------------------------------------------------- geometry
 // Restatement of the res_domain.f90 decomposition used by every reservoir of the

@@ -303,7 +303,7 @@ __device__ inline Quad<WT> load_quad(const WT *p) {
 //
 // wflag (may be null): the forecast grids come from another stream, whose one-lane
 // signal kernel stores a sequence number >= wval behind SPEEDY's exit (SML_HOP_KERNEL;
-// sml_hybrid.hip k_hop_signal).  The kernel then goes in ahead of the forecast: its
+// sml_hops.hpp k_hop_signal).  The kernel then goes in ahead of the forecast: its
 // W_out(:, 1:ncs) block, the gather's tables and mean / std are loaded while the window
 // still runs, and only the forecast values wait -- one relaxed poll by one lane,
 // one agent-scope acquire by that wave, a barrier (MI355X_MICROARCH.md

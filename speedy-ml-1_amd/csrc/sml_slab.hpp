@@ -5,7 +5,7 @@
 // entries once and serves every member with them, a tile of kSlabTile members at a time:
 // the tile's loads are independent, so they are in flight together.  The arithmetic per
 // member is the single-member loop's, operation for operation; that loop runs these
-// kernels at E = 1 (sml_hybrid.hip).  Plain vector loads and stores only: no block waits
+// kernels at E = 1 (through sml_slab.hip).  Plain vector loads and stores only: no block waits
 // for another, and nothing is shared between threads.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -2,7 +2,7 @@
 !> independent of SPEEDY's: the module's `calendar`, initialize_calendar (start date
 !> only, as the reference: the current date is left as it was) and
 !> get_current_time_delta_hour.  The arithmetic is the library's
-!> sml_calendar_delta_hour (csrc/sml_hybrid.hip, with the reference's quirks: years of
+!> sml_calendar_delta_hour (csrc/sml_hybrid_layout.cpp, with the reference's quirks: years of
 !> 8760 h, the elapsed leap days subtracted, an exact month boundary falling to the
 !> last day of the month before); the reference's SAVEd month table -- February
 !> latched at 29 days once a leap year is met -- is this module's `feb29_latch`,

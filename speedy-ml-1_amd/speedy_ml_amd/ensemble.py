@@ -51,6 +51,7 @@ import torch
 
 from ._lib import SmlError, check, lib, ptr
 from .dynamics import ALPH, DELT
+from .hybrid import slab_state_copy
 
 
 def _member_stride(a, shape, what):
@@ -390,13 +391,7 @@ class EnsembleLoop:
         check(lib().sml_slab_buffers(self._slab_h, *args))
         cols, n = ctypes.c_int(), ctypes.c_int()
         check(lib().sml_slab_info(self._slab_h, None, None, None, ctypes.byref(cols), ctypes.byref(n), None))
-        out = {"sst": np.zeros((48, 96)), "ring": np.zeros((cols.value, n.value)), "feedback": np.zeros(n.value),
-               "outvec": np.zeros((self.slab.res.nlocal, 4))}
-        for key, src, stride in zip(("sst", "ring", "feedback", "outvec"), p, st):
-            a = out[key]
-            if a.size:
-                check(lib().sml_copy_to_host(ptr(a), ctypes.c_void_p(src.value + 8 * e * stride.value), a.nbytes))
-        return out
+        return slab_state_copy(p, [s.value for s in st], e, cols.value, n.value, self.slab.res.nlocal)
 
     def step(self):
         """One hybrid time step of every member.  Returns when the E windows are done; the

@@ -173,21 +173,13 @@ class HybridLoop:
         """Host copies of the loop's slab state (after its work completes):
         wholegrid_sst [48, 96], the ring [ratio - 1, tot], the last slab feedback [tot]
         and slab outvecs [nslab, 4]."""
-        import numpy as np
-
         sst, ring, fb, ov = (ctypes.c_void_p() for _ in range(4))
         n = ctypes.c_int()
         check(lib().sml_hybrid_slab_buffers(self._h, ctypes.byref(sst), ctypes.byref(ring), ctypes.byref(n),
                                             ctypes.byref(fb), ctypes.byref(ov)))
         sl = self.slab
-        ratio = sl.timestep_slab // sl.timestep
-        out = {"sst": np.zeros((48, 96)), "ring": np.zeros((ratio - 1, n.value)), "feedback": np.zeros(n.value),
-               "outvec": np.zeros((sl.res.nlocal, 4))}
-        for key, src in (("sst", sst), ("ring", ring), ("feedback", fb), ("outvec", ov)):
-            a = out[key]
-            if a.size:
-                check(lib().sml_copy_to_host(ptr(a), src, a.nbytes))
-        return out
+        return slab_state_copy((sst, ring, fb, ov), (0, 0, 0, 0), 0, sl.timestep_slab // sl.timestep - 1, n.value,
+                               sl.res.nlocal)
 
     def predict(self):
         """First half of a step: this rank's outvecs into `ov` (on `xstream`)."""
@@ -247,3 +239,17 @@ class SlabOcean:
         self.res, self.base_sst, self.sea_mask = res, base_sst, sea_mask
         self.timestep, self.timestep_slab, self.sst_bias = timestep, timestep_slab, sst_bias
 
+
+def slab_state_copy(ptrs, strides, member, ring_columns, ring_len, nslab):
+    """Host copies of one member's slab state from the four device buffers `ptrs` (the sst
+    grid, the ring, the slab feedback, the slab outvecs; c_void_p) and their member strides
+    in doubles: {"sst": [48, 96], "ring": [ring_columns, ring_len], "feedback": [ring_len],
+    "outvec": [nslab, 4]}.  Synchronous (sml_copy_to_host)."""
+    import numpy as np
+
+    out = {"sst": np.zeros((48, 96)), "ring": np.zeros((ring_columns, ring_len)), "feedback": np.zeros(ring_len),
+           "outvec": np.zeros((nslab, 4))}
+    for a, src, stride in zip(out.values(), ptrs, strides):
+        if a.size:
+            check(lib().sml_copy_to_host(ptr(a), ctypes.c_void_p(src.value + 8 * member * int(stride)), a.nbytes))
+    return out
