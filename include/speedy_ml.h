@@ -769,6 +769,54 @@ int sml_res_tile_feedback_members(sml_reservoirs *c, const double *d_grid4d, int
                                   const double *d_tisr, double *d_feedback, int64_t fb_stride, void *stream);
 int sml_res_tile_tisr_field_members(sml_reservoirs *c, const double *d_tisr_grid, double *d_feedback,
                                     int64_t fb_stride, void *stream);
+/* ---- the training front end: from a series of global grids to standardised blocks
+ * (get_training_data's standardize_data_5d_logp_tisr / standardize_data_3d /
+ * standardize_sst_data_3d, mod_utilities.f90:846-905, :1137-1186, and the tiling of the
+ * truth and the SPEEDY forecasts).  Step t of a series starts t * stride doubles in:
+ * d_g4 [T][8][48][96][4] with g4_stride; d_g2 (logp), d_pr (precipitation, in the form
+ * sml_res_tile_feedback's d_precip has), d_sst, d_tisr [T][48][96] with g2_stride.
+ *
+ * sml_res_series_stats: for every local region i and slot l of the 36, over the grid
+ * sources P of the region's feedback entries of that slot (slots 0..31 = v * 8 + z of the
+ * 4-d grid, 32 logp, 34 precip, 33 tisr, 35 sst: the region's input tile) and N = T |P|,
+ *     mean = (sum_t sum_p x_t[p]) / N,  std = sqrt(sum_t sum_p (x_t[p] - mean)^2 / N),
+ * the population, two-pass form, for every slot: the reference's one-pass precipitation
+ * statistic is deliberately not copied (ill-conditioned; equal mathematically).  No
+ * guards: a constant field gives std 0 up to the sums' rounding.  d_meanstd [nlocal][72]
+ * device doubles, mean then std, the context's own layout.  Slot 35 of a region without the
+ * sst flag, and slot 33 when d_tisr is NULL, get mean 0 and std 1.  d_sst may be NULL iff
+ * no local region has the sst flag.  d_sst_change [nlocal] device ints (may be NULL):
+ * 1 iff sum (x - mean)^2 > 0 and std > 0.2 for the sst slot -- the reference's rule for
+ * keeping the sst input, reported and not acted on (ninp is fixed at create); 0 for a
+ * region without the flag.  Three launches on `stream` (two streaming passes over the
+ * series per grid point, T split in chunks that depend on T alone, then a combine per
+ * (region, slot)), no atomics, no host synchronisation: the same bits on any stream.  The
+ * workspace (44 MB) is the context's, allocated at the first call.
+ * SML_ERR_ARG with a message, before anything is enqueued: T < 1; g4_stride < 8*48*96*4
+ * or g2_stride < 48*96; d_g4 or g4_stride off 16-byte alignment; a NULL context, d_g4,
+ * d_g2, d_pr or d_meanstd; a sml_res_create_generic context. */
+int sml_res_series_stats(sml_reservoirs *c, const double *d_g4, int64_t g4_stride, const double *d_g2,
+                         const double *d_pr, const double *d_sst, const double *d_tisr, int64_t g2_stride, int T,
+                         double *d_meanstd, int *d_sst_change, void *stream);
+/* adopt a [nlocal][72] device table (sml_res_series_stats' layout) as the context's mean
+ * / std: the device table every kernel standardises with and the host copy
+ * sml_res_mean_std returns.  Copies on `stream` and synchronises it.  SML_ERR_ARG inside
+ * a begun step (sml_res_step_begun) and on a context with members > 1. */
+int sml_res_set_mean_std_device(sml_reservoirs *c, const double *d_meanstd, void *stream);
+/* T input blocks and T model blocks in one launch each.  Input block t, at d_inputs +
+ * t * in_stride (in_stride >= the total feedback: the layout sml_res_synchronize and
+ * sml_res_train_drive read), is bit for bit sml_res_tile_feedback with d_tisr = NULL, then
+ * sml_res_tile_tisr_field on step t's tisr field, on step t's grids; its sst entries, which
+ * those calls leave alone, are (sst_t[p] - mean[35]) / std[35] at the tisr entries' points.
+ * d_sst / d_tisr NULL: those entries are left untouched.  Model block t [nlocal][ncs], at
+ * d_model + t * model_stride, is bit for bit sml_res_tile_local_model on d_fc4 + t *
+ * fc4_stride, d_fc2 + t * fc2_stride.  d_fc4, d_fc2 and d_model are NULL together, and
+ * must be NULL at chunk_speedy == 0.  Words between blocks are not written.  Checks as
+ * sml_res_series_stats, and every stride against its packed size.  Stream-ordered. */
+int sml_res_tile_series(sml_reservoirs *c, const double *d_g4, int64_t g4_stride, const double *d_g2,
+                        const double *d_pr, const double *d_sst, const double *d_tisr, int64_t g2_stride,
+                        const double *d_fc4, int64_t fc4_stride, const double *d_fc2, int64_t fc2_stride, int T,
+                        double *d_inputs, int64_t in_stride, double *d_model, int64_t model_stride, void *stream);
 /* the loop's main (reservoir + exchange) and side (SPEEDY) streams */
 int sml_hybrid_streams(const sml_hybrid *h, void **main, void **side);
 /* the CU split of the two streams: SPEEDY's CUs [0, speedy_cus) and the reservoir's

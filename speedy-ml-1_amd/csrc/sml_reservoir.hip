@@ -53,6 +53,7 @@ SML_TL_DEFINE(reservoir)
 #include "sml_res_drive.hpp"
 #include "sml_res_radius.hpp"
 #include "sml_res_tiling.hpp"
+#include "sml_res_series.hpp"
 #include "sml_res_readout.hpp"
 #include "sml_res_members.hpp"
 // clang-format on
@@ -173,6 +174,12 @@ struct sml_reservoirs : PoolPlan {
     uint16_t *d_tisr_reg = nullptr;
     int32_t *d_lm_src = nullptr;    // [nlocal*ncs]
     uint8_t *d_lm_l = nullptr;
+    // the series calls (sml_res_series_stats, sml_res_tile_series): their tables
+    // (build_series_tables) and the statistics' workspace, allocated at the first such call
+    int32_t *d_ser_src = nullptr, *d_ser_pt_off = nullptr, *d_ser_pt_grid = nullptr;
+    uint8_t *d_ser_l = nullptr;
+    unsigned char *d_ser_sst = nullptr;  // [nlocal] the regions' sst flags
+    double *d_ser_work = nullptr;        // SeriesWork: (2 * kSerSplitMax + 1) * kSerPoints doubles
     double *d_io = nullptr;         // staging for sml_res_step_host
     size_t d_io_n = 0;
     StepEvents timers;
@@ -1668,6 +1675,127 @@ extern "C" int sml_res_tile_inputs(sml_reservoirs *c, const double *d_grid4d, co
                                    const double *d_tisr, double *d_feedback, double *d_local_model, void *stream) {
     if (int rc = sml_res_tile_feedback(c, d_grid4d, d_grid2d, d_precip, d_tisr, d_feedback, stream)) return rc;
     if (c->ncs && d_fc4d && c->nlocal) return sml_res_tile_local_model(c, d_fc4d, d_fc2d, d_local_model, stream);
+    return SML_OK;
+}
+
+// ---------------------------------------------------------------- series of grids
+namespace {
+
+// the series calls' tables, at the first of them (ordered before every launch: synchronous uploads)
+int ensure_series_tables(sml_reservoirs *c) {
+    if (c->d_ser_src) return SML_OK;
+    const TablesIn in{c->numregions, c->nlocal, c->ncs, c->nout, c->geom.data(), c->sst.data(), c->ninp.data(),
+                      c->rd.data(), c->tot_fb, nullptr};
+    SeriesTables t;
+    if (int rc = build_series_tables(in, &t)) return rc;
+    auto mk = [c](auto **d, const auto &v) {
+        const int rc = pool(c, d, (int64_t)v.size());
+        return rc ? rc : upload(*d, v);
+    };
+    int rc;
+    if ((rc = mk(&c->d_ser_l, t.l)) || (rc = mk(&c->d_ser_pt_off, t.pt_off)) ||
+        (rc = mk(&c->d_ser_pt_grid, t.pt_grid)) || (rc = mk(&c->d_ser_sst, c->sst)) || (rc = mk(&c->d_ser_src, t.src)))
+        return rc;
+    return SML_OK;
+}
+
+// what the two series calls check of their common arguments, before anything is enqueued
+int check_series_args(const sml_reservoirs *c, const double *d_g4, int64_t g4_stride, const double *d_g2,
+                      const double *d_pr, int64_t g2_stride, int T) {
+    SML_REQUIRE(T >= 1, "T = %d: a series holds one step at least", T);
+    SML_REQUIRE(g4_stride >= kGrid4d, "g4_stride %lld smaller than the 4-d grid's %d doubles", (long long)g4_stride,
+                kGrid4d);
+    SML_REQUIRE(g2_stride >= kGrid2d, "g2_stride %lld smaller than a 2-d grid's %d doubles", (long long)g2_stride,
+                kGrid2d);
+    SML_REQUIRE(g4_stride % 2 == 0, "g4_stride %lld is odd: every step's 4-d grid must be 16-byte aligned",
+                (long long)g4_stride);
+    SML_REQUIRE(c != nullptr, "null reservoir context");
+    SML_REQUIRE(d_g4 && d_g2 && d_pr, "null argument (d_g4, d_g2 and d_pr are needed)");
+    SML_REQUIRE((uintptr_t)d_g4 % 16 == 0, "d_g4 %p is not 16-byte aligned", (const void *)d_g4);
+    SML_REQUIRE(!c->generic, "a generic (slab) context has no exchange tables");
+    return SML_OK;
+}
+
+}  // namespace
+
+extern "C" int sml_res_series_stats(sml_reservoirs *c, const double *d_g4, int64_t g4_stride, const double *d_g2,
+                                    const double *d_pr, const double *d_sst, const double *d_tisr,
+                                    int64_t g2_stride, int T, double *d_meanstd, int *d_sst_change, void *stream) {
+    if (int rc = check_series_args(c, d_g4, g4_stride, d_g2, d_pr, g2_stride, T)) return rc;
+    SML_REQUIRE(d_meanstd, "d_meanstd is null");
+    bool any_sst = false;
+    for (int i = 0; i < c->nlocal; ++i) any_sst = any_sst || c->sst[i];
+    SML_REQUIRE(d_sst || !any_sst, "d_sst is null on a context with sst regions");
+    if (!c->nlocal) return SML_OK;
+    if (int rc = ensure_series_tables(c)) return rc;
+    if (!c->d_ser_work)
+        if (int rc = pool(c, &c->d_ser_work, (int64_t)(2 * kSerSplitMax + 1) * kSerPoints)) return rc;
+    const SeriesSplit sp = series_split(T);
+    const SeriesIn in{d_g4, {d_g2, d_pr, any_sst ? d_sst : nullptr, d_tisr}, g4_stride, g2_stride};
+    const SeriesWork w{c->d_ser_work, c->d_ser_work + (size_t)kSerSplitMax * kSerPoints,
+                       c->d_ser_work + (size_t)(kSerSplitMax + 1) * kSerPoints};
+    const dim3 grid(kSerQuadBlocks + kSerFields2d * kSerPointBlocks, sp.S);
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(k_series_sum, grid, dim3(kSerThreads), 0, st, in, w, T, sp.len);
+    hipLaunchKernelGGL(k_series_m2, grid, dim3(kSerThreads), 0, st, in, w, T, sp.len, sp.S);
+    const int total = c->nlocal * kMeanStd;
+    hipLaunchKernelGGL(k_series_combine, dim3((total + 63) / 64), dim3(64), 0, st, c->d_ser_pt_off, c->d_ser_pt_grid,
+                       c->d_ser_sst, w, any_sst ? 1 : 0, d_tisr ? 1 : 0, T, sp.S, c->nlocal, d_meanstd, d_sst_change);
+    SML_HIP(hipGetLastError());
+    return SML_OK;
+}
+
+extern "C" int sml_res_set_mean_std_device(sml_reservoirs *c, const double *d_meanstd, void *stream) {
+    SML_REQUIRE(c != nullptr, "null reservoir context");
+    SML_REQUIRE(d_meanstd, "d_meanstd is null");
+    SML_REQUIRE(!c->is_begun(), "sml_res_set_mean_std_device inside a begun step");
+    SML_REQUIRE(c->members == 1, "sml_res_set_mean_std_device on a context of %d members", c->members);
+    if (!c->nlocal) return SML_OK;
+    const size_t bytes = (size_t)c->nlocal * 2 * kMeanStd * sizeof(double);
+    hipStream_t st = (hipStream_t)stream;
+    SML_HIP(hipMemcpyAsync(c->d_meanstd, d_meanstd, bytes, hipMemcpyDeviceToDevice, st));
+    SML_HIP(hipMemcpyAsync(c->meanstd_h.data(), d_meanstd, bytes, hipMemcpyDeviceToHost, st));
+    SML_HIP(hipStreamSynchronize(st));
+    return SML_OK;
+}
+
+extern "C" int sml_res_tile_series(sml_reservoirs *c, const double *d_g4, int64_t g4_stride, const double *d_g2,
+                                   const double *d_pr, const double *d_sst, const double *d_tisr, int64_t g2_stride,
+                                   const double *d_fc4, int64_t fc4_stride, const double *d_fc2, int64_t fc2_stride,
+                                   int T, double *d_inputs, int64_t in_stride, double *d_model,
+                                   int64_t model_stride, void *stream) {
+    if (int rc = check_series_args(c, d_g4, g4_stride, d_g2, d_pr, g2_stride, T)) return rc;
+    SML_REQUIRE(d_inputs, "d_inputs is null");
+    SML_REQUIRE(in_stride >= c->tot_fb, "in_stride %lld smaller than the packed feedback's %lld doubles",
+                (long long)in_stride, (long long)c->tot_fb);
+    const int nmod = (d_fc4 ? 1 : 0) + (d_fc2 ? 1 : 0) + (d_model ? 1 : 0);
+    SML_REQUIRE(nmod == 0 || nmod == 3, "d_fc4, d_fc2 and d_model are given together or not at all");
+    SML_REQUIRE(nmod == 0 || c->ncs > 0, "model blocks on a context with chunk_speedy 0");
+    if (nmod) {
+        SML_REQUIRE(fc4_stride >= kGrid4d, "fc4_stride %lld smaller than the 4-d grid's %d doubles",
+                    (long long)fc4_stride, kGrid4d);
+        SML_REQUIRE(fc2_stride >= kGrid2d, "fc2_stride %lld smaller than a 2-d grid's %d doubles",
+                    (long long)fc2_stride, kGrid2d);
+        SML_REQUIRE(model_stride >= (int64_t)c->nlocal * c->ncs,
+                    "model_stride %lld smaller than the packed model block's %lld doubles", (long long)model_stride,
+                    (long long)c->nlocal * c->ncs);
+    }
+    if (!c->nlocal) return SML_OK;
+    if (int rc = ensure_series_tables(c)) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    if (c->tot_fb) {
+        const SeriesIn in{d_g4, {d_g2, d_pr, d_sst, d_tisr}, g4_stride, g2_stride};
+        const int total = (int)c->tot_fb;
+        hipLaunchKernelGGL(k_tile_series, dim3((total + 255) / 256), dim3(256), 0, st, c->d_ser_src, c->d_ser_l,
+                           c->d_fb_reg, c->d_meanstd, in, d_inputs, in_stride, total, T);
+    }
+    if (nmod) {
+        const int total = c->nlocal * c->ncs;
+        hipLaunchKernelGGL(k_tile_series_model, dim3((total + 255) / 256), dim3(256), 0, st, c->d_lm_src, c->d_lm_l,
+                           c->d_meanstd, d_fc4, fc4_stride, d_fc2, fc2_stride, d_model, model_stride, c->ncs, total,
+                           T);
+    }
+    SML_HIP(hipGetLastError());
     return SML_OK;
 }
 

@@ -383,6 +383,44 @@ int build_region_tables(const TablesIn &in, RegionTables *out) {
     return SML_OK;
 }
 
+int build_series_tables(const TablesIn &in, SeriesTables *out) {
+    *out = SeriesTables();
+    SML_REQUIRE(!in.out_l, "a generic (slab) context has no exchange tables");
+    out->src.assign(in.tot_fb, 0);
+    out->l.assign(in.tot_fb, 0);
+    out->pt_off.assign(in.nlocal + 1, 0);
+    for (int i = 0; i < in.nlocal; ++i) {
+        const RegionGeom &g = in.geom[i];
+        const int ix = g.inx, iy = g.iny, in2d = ix * iy, natmo = kVars * in2d * kZGrid;
+        const int64_t base = in.rd[i].fb;
+        SML_REQUIRE(base + region_ninp(g, in.sst[i] != 0) <= in.tot_fb, "region %d: feedback past the pool", i);
+        // the 2-d blocks behind the atmosphere's, in the feedback's order (region_ninp)
+        int blocks = 0, field[4], slot[4];
+        field[blocks] = kSerLogp, slot[blocks++] = 32;
+        field[blocks] = kSerPrecip, slot[blocks++] = 34;
+        if (in.sst[i]) field[blocks] = kSerSst, slot[blocks++] = 35;
+        field[blocks] = kSerTisr, slot[blocks++] = 33;
+        for (int ly = 0; ly < iy; ++ly)
+            for (int lx = 0; lx < ix; ++lx) {
+                const int gx = input_x(g, lx + 1) - 1, gy = g.in_ystart - 1 + ly, p = lx + ix * ly;
+                out->pt_grid.push_back(g2(gx, gy));
+                for (int z = 0; z < kZGrid; ++z)
+                    for (int v = 0; v < kVars; ++v) {
+                        const int64_t e = base + v + kVars * (p + in2d * z);
+                        out->src[e] = g4(v, gx, gy, z);
+                        out->l[e] = (uint8_t)(v * kZGrid + z);
+                    }
+                for (int b = 0; b < blocks; ++b) {
+                    const int64_t e = base + natmo + (int64_t)b * in2d + p;
+                    out->src[e] = kGrid4d + field[b] * kGrid2d + g2(gx, gy);
+                    out->l[e] = (uint8_t)slot[b];
+                }
+            }
+        out->pt_off[i + 1] = (int32_t)out->pt_grid.size();
+    }
+    return SML_OK;
+}
+
 std::vector<int32_t> block_first_regions(const std::vector<int32_t> &row0, int G) {
     const int64_t total = row0.back();
     std::vector<int32_t> r0(G);

@@ -1,8 +1,10 @@
 // sml_reservoir_layout.hpp -- the reservoir context's weight layout and index tables:
 // what sml_reservoir.hip uploads, computed on the host with no HIP call in between, so
-// the index arithmetic runs (and is sanitised) on a CPU: tests/reservoir_layout_check.cpp.
+// the index arithmetic runs (and is sanitised) on a CPU: tests/reservoir_layout_check.cpp,
+// tests/series_layout_check.cpp.
 #pragma once
 
+#include <algorithm>
 #include <cstdint>
 #include <vector>
 
@@ -224,6 +226,39 @@ struct RegionTables {
 };
 
 int build_region_tables(const TablesIn &in, RegionTables *out);
+
+// ------------------------------------------------------------------ series tables
+// One step of a training series as one index space (sml_res_series_stats,
+// sml_res_tile_series): the 4-d grid's kGrid4d doubles, then the four 2-d fields of
+// kGrid2d points each in the order of kSer*.  A field has a pointer of its own: the
+// index names the field and the point, not an address.
+constexpr int kSerLogp = 0, kSerPrecip = 1, kSerSst = 2, kSerTisr = 3, kSerFields2d = 4;
+constexpr int kSerPoints = kGrid4d + kSerFields2d * kGrid2d;  // 165888
+
+// the statistics' split of T steps into S chunks of at most `len` steps (none empty):
+// a function of T alone, so the summation order depends on nothing else
+constexpr int kSerChunkMin = 16;  // steps a chunk holds before T is split further
+constexpr int kSerSplitMax = 16;  // chunks at most
+struct SeriesSplit {
+    int S, len;
+};
+inline SeriesSplit series_split(int T) {
+    const int want = std::min(kSerSplitMax, (T + kSerChunkMin - 1) / kSerChunkMin);
+    const int len = (T + std::max(want, 1) - 1) / std::max(want, 1);
+    return {len > 0 ? (T + len - 1) / len : 0, len};
+}
+
+// what build_region_tables does not hold: every feedback entry's source in the series'
+// index space -- the sst and tisr entries included, which the single-grid tables leave to
+// other stages -- with its mean / std slot, and each local region's input-tile points
+struct SeriesTables {
+    std::vector<int32_t> src;     // [tot_fb] series index; an sst entry of an unflagged region does not exist
+    std::vector<uint8_t> l;       // [tot_fb] slot: v * 8 + z, 32 logp, 34 precip, 35 sst, 33 tisr
+    std::vector<int32_t> pt_off;  // [nlocal + 1] region i's points: pt_grid[pt_off[i] .. pt_off[i + 1])
+    std::vector<int32_t> pt_grid; // 2-d grid index of each input-tile point, in the tile's (x fastest) order
+};
+
+int build_series_tables(const TablesIn &in, SeriesTables *out);
 
 // mean/std index (0-based) of output o of the bottom-level 2x2 reservoir:
 // atmo (var,x,y,z) -> (var-1)*8+z, logp -> 33, precip -> 35 (1-based; :1815-1846)

@@ -836,6 +836,36 @@ module sml_hip
       integer(c_int64_t), value :: stride, model_stride
       integer(c_int) :: rc
     end function
+    !> the training front end on a series of global grids (get_training_data's statistics
+    !> and tilings; include/speedy_ml.h): step t of a series starts t * stride doubles in.
+    !> d_meanstd [nlocal][72] device doubles, mean then std; d_sst_change [nlocal] device
+    !> ints (or c_null_ptr); d_sst / d_tisr may be c_null_ptr as the header says
+    function sml_res_series_stats(ctx, d_g4, g4_stride, d_g2, d_pr, d_sst, d_tisr, g2_stride, t, d_meanstd, &
+        d_sst_change, stream) bind(C, name='sml_res_series_stats') result(rc)
+      import :: c_ptr, c_int, c_int64_t
+      type(c_ptr), value :: ctx, d_g4, d_g2, d_pr, d_sst, d_tisr, d_meanstd, d_sst_change, stream
+      integer(c_int64_t), value :: g4_stride, g2_stride
+      integer(c_int), value :: t
+      integer(c_int) :: rc
+    end function
+    !> adopt a [nlocal][72] device table as the context's mean / std (synchronises the stream)
+    function sml_res_set_mean_std_device(ctx, d_meanstd, stream) &
+        bind(C, name='sml_res_set_mean_std_device') result(rc)
+      import :: c_ptr, c_int
+      type(c_ptr), value :: ctx, d_meanstd, stream
+      integer(c_int) :: rc
+    end function
+    !> t standardised input blocks (in_stride apart) and t model blocks [nlocal][ncs]
+    !> (model_stride apart; d_fc4, d_fc2, d_model c_null_ptr together), one launch each
+    function sml_res_tile_series(ctx, d_g4, g4_stride, d_g2, d_pr, d_sst, d_tisr, g2_stride, d_fc4, fc4_stride, &
+        d_fc2, fc2_stride, t, d_inputs, in_stride, d_model, model_stride, stream) &
+        bind(C, name='sml_res_tile_series') result(rc)
+      import :: c_ptr, c_int, c_int64_t
+      type(c_ptr), value :: ctx, d_g4, d_g2, d_pr, d_sst, d_tisr, d_fc4, d_fc2, d_inputs, d_model, stream
+      integer(c_int64_t), value :: g4_stride, g2_stride, fc4_stride, fc2_stride, in_stride, model_stride
+      integer(c_int), value :: t
+      integer(c_int) :: rc
+    end function
     !> the spectral radius of every local region's A (gen_res's sparse_eigen,
     !> mod_reservoir.f90:190): lo <= rho <= hi per region, info 0 when hi - lo <= tol * hi;
     !> host arrays of nlocal, filled when the call returns

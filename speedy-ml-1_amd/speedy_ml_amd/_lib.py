@@ -74,6 +74,7 @@ EXPORTED = (
     "sml_slab_ring", "sml_slab_buffers",
     "sml_ens_create", "sml_ens_destroy", "sml_ens_info", "sml_ens_reset", "sml_ens_moments", "sml_ens_scores",
     "sml_ens_read", "sml_ens_weights",
+    "sml_res_series_stats", "sml_res_set_mean_std_device", "sml_res_tile_series",
 )
 
 SML_HOP_AUTO, SML_HOP_WAIT_VALUE, SML_HOP_EVENTS, SML_HOP_KERNEL = 0, 1, 2, 3
@@ -313,6 +314,9 @@ def _declare(L: ctypes.CDLL) -> None:
         "sml_ens_scores": [vp, vp, i64, vp, vp, i64, vp, vp, vp, i, vp],
         "sml_ens_read": [vp, i, i, vp, vp],
         "sml_ens_weights": [vp],
+        "sml_res_series_stats": [vp, vp, i64, vp, vp, vp, vp, i64, i, vp, vp, vp],
+        "sml_res_set_mean_std_device": [vp, vp, vp],
+        "sml_res_tile_series": [vp, vp, i64, vp, vp, vp, vp, i64, vp, i64, vp, i64, i, vp, i64, vp, i64, vp],
     }
     for name, args in sig.items():
         if os.environ.get("SML_LIB") and not hasattr(L, name):

@@ -10,6 +10,11 @@ Layouts (C order of the reference's Fortran arrays): per region S is
 augmented_states(naug, m) == C (m, naug), T is targetdata(nout, m) == C (m, nout),
 W_out is wout(nout, naug) == C (naug, nout).  Device buffers are float64 CUDA
 tensors packing the regions back to back.
+
+The front end (get_training_data: the standardisation statistics and the tiling of the
+truth and the SPEEDY forecasts) runs on the device too, from a series of global grids:
+fit_standardisation, tile_series, train_from_grids (sml_res_series_stats,
+sml_res_set_mean_std_device, sml_res_tile_series).
 """
 from __future__ import annotations
 
@@ -87,6 +92,39 @@ class Trainer:
         return G, B
 
 
+def _fit_wout(res, blocks, sync_chunk: int, discard: int, batch: int, nbatches: int, ncs: int, beta_res: float,
+              beta_model: float, using_prior: bool, prior_val: float, dtype, device, stream):
+    """The loop train_wout and train_from_grids share: states to zero, the discard phase
+    (Reservoirs.synchronize over at most sync_chunk blocks a call), per batch one
+    Reservoirs.train_drive + Trainer.accumulate, then Trainer.solve.  blocks(t0, m): the
+    packed input blocks t0 .. t0 + m - 1 and their model blocks (None when ncs == 0)."""
+    import torch
+
+    naug = [ncs + int(n) for n in res.n]
+    for i, n in enumerate(res.n):
+        res.set_state(i, np.zeros(int(n)))
+    if discard == 0:
+        res.synchronize(blocks(0, 0)[0], 0, stream=stream)
+    t = 0
+    while t < discard:
+        m = min(sync_chunk, discard - t)
+        res.synchronize(blocks(t, m)[0], m, stream=stream)
+        t += m
+    tr = Trainer(naug, res.nout)
+    tr.reset(stream=stream)
+    states = torch.empty(sum(naug) * batch, dtype=torch.float64, device=device)
+    targets = torch.empty(len(naug) * batch * res.nout, dtype=torch.float64, device=device)
+    for b in range(nbatches):
+        d_in, d_mod = blocks(discard + b * batch, batch)
+        res.train_drive(d_in, batch, d_mod if ncs else None, states, targets, stream=stream)
+        tr.accumulate(states, targets, batch, stream=stream)
+    packed, info = tr.solve(ncs=ncs, beta_res=beta_res, beta_model=beta_model, using_prior=using_prior,
+                            prior_val=prior_val, stream=stream)
+    wouts = [v.cpu().numpy().astype(dtype) for v in tr.wout_views(packed)]
+    tr.close()
+    return wouts, info
+
+
 def train_wout(res, d_inputs, d_model, discard: int, batch: int, nbatches: int, ncs: int = 132,
                beta_res: float = 0.001, beta_model: float = 1.0, using_prior: bool = True, prior_val: float = 0.0,
                dtype=np.float32, stream=None):
@@ -107,8 +145,6 @@ def train_wout(res, d_inputs, d_model, discard: int, batch: int, nbatches: int, 
     of the file's wout(nout, ncs + n), NF90_REAL, ready for write_region_netcdf /
     Reservoirs.load_region -- and the per-region potrf info.  dtype=np.float64 keeps
     the solve's own precision (the float32 arrays are its rounding)."""
-    import torch
-
     if ncs != res.ncs:
         raise ValueError(f"ncs {ncs} differs from the context's chunk_speedy {res.ncs}")
     nblocks = discard + batch * nbatches
@@ -121,21 +157,169 @@ def train_wout(res, d_inputs, d_model, discard: int, batch: int, nbatches: int, 
         d_model = d_model.reshape(-1)
         if d_model.numel() < nblocks * nmod:
             raise ValueError("d_model holds fewer than discard + batch * nbatches model blocks")
-    naug = [ncs + int(n) for n in res.n]
-    for i, n in enumerate(res.n):
-        res.set_state(i, np.zeros(int(n)))
-    res.synchronize(d_inputs, discard, stream=stream)
-    tr = Trainer(naug, res.nout)
-    tr.reset(stream=stream)
-    states = torch.empty(sum(naug) * batch, dtype=torch.float64, device=d_inputs.device)
-    targets = torch.empty(len(naug) * batch * res.nout, dtype=torch.float64, device=d_inputs.device)
-    for b in range(nbatches):
-        t0 = discard + b * batch
-        res.train_drive(d_inputs[t0 * tot:], batch, d_model[t0 * nmod:] if ncs else None, states, targets,
-                        stream=stream)
-        tr.accumulate(states, targets, batch, stream=stream)
-    packed, info = tr.solve(ncs=ncs, beta_res=beta_res, beta_model=beta_model, using_prior=using_prior,
-                            prior_val=prior_val, stream=stream)
-    wouts = [v.cpu().numpy().astype(dtype) for v in tr.wout_views(packed)]
-    tr.close()
-    return wouts, info
+
+    def blocks(t0, m):
+        return d_inputs[t0 * tot:], (d_model[t0 * nmod:] if ncs else None)
+
+    return _fit_wout(res, blocks, max(discard, 1), discard, batch, nbatches, ncs, beta_res, beta_model, using_prior,
+                     prior_val, dtype, d_inputs.device, stream)
+
+
+# ---- from a series of global grids (sml_res_series_stats, sml_res_tile_series)
+G4_SHAPE, G2_SHAPE = (8, 48, 96, 4), (48, 96)
+
+
+def _series(t, what, shape):
+    """A float64 device series [T, *shape] whose steps are dense: (T, its step stride)."""
+    import torch
+
+    if t.dtype != torch.float64 or not t.is_cuda:
+        raise ValueError(f"{what}: a float64 device tensor expected")
+    if t.dim() != len(shape) + 1 or tuple(t.shape[1:]) != tuple(shape) or t.shape[0] < 1:
+        raise ValueError(f"{what}: shape (T,) + {tuple(shape)} expected, got {tuple(t.shape)}")
+    if not t[0].is_contiguous():
+        raise ValueError(f"{what}: a step's grid must be packed, got strides {t.stride()}")
+    packed = int(np.prod(shape))
+    stride = int(t.stride(0)) if t.shape[0] > 1 else packed
+    if stride < packed:
+        raise ValueError(f"{what}: the step stride {stride} is below the packed {packed}")
+    return int(t.shape[0]), stride
+
+
+def _truth_series(g4, g2, pr, sst, tisr):
+    """(T, g4 stride, common stride of the 2-d series)."""
+    T, s4 = _series(g4, "g4", G4_SHAPE)
+    s2 = None
+    for name, a in (("g2", g2), ("pr", pr), ("sst", sst), ("tisr", tisr)):
+        if a is None:
+            continue
+        Ta, sa = _series(a, name, G2_SHAPE)
+        if Ta != T:
+            raise ValueError(f"{name}: {Ta} steps, g4 has {T}")
+        if T > 1 and s2 is not None and sa != s2:
+            raise ValueError(f"{name}: step stride {sa}, the 2-d series share one ({s2})")
+        s2 = sa if s2 is None else s2
+    return T, s4, s2
+
+
+def series_stats(res, g4, g2, pr, sst=None, tisr=None, stream=None):
+    """sml_res_series_stats: the [nlocal, 72] device table (mean then std per region) and
+    the [nlocal] device int32 sst_change of a series g4 [T, 8, 48, 96, 4], g2 / pr / sst /
+    tisr [T, 48, 96] (the 2-d series with one common step stride).  Stream-ordered."""
+    import torch
+
+    T, s4, s2 = _truth_series(g4, g2, pr, sst, tisr)
+    table = torch.empty((res.nlocal, 72), dtype=torch.float64, device=g4.device)
+    change = torch.zeros(res.nlocal, dtype=torch.int32, device=g4.device)
+    check(lib().sml_res_series_stats(res.handle, ptr(g4), s4, ptr(g2), ptr(pr), ptr(sst), ptr(tisr), s2, T, ptr(table),
+                                     ptr(change), stream_ptr(stream)))
+    return table, change
+
+
+def fit_standardisation(res, g4, g2, pr, sst=None, tisr=None, adopt: bool = True, stream=None):
+    """The standardisation statistics of every local region of `res` over a series of
+    global grids (get_training_data's standardize_data_5d_logp_tisr, standardize_data_3d,
+    standardize_sst_data_3d), computed on the device.  Returns (mean [nlocal, 36],
+    std [nlocal, 36], sst_change [nlocal]) as numpy arrays; adopt=True makes them the
+    context's (sml_res_set_mean_std_device).  Raises ValueError naming the local regions
+    whose sst flag is set while sst_change is 0 (the reference would drop their sst
+    input; a context's ninp is fixed at create), before anything is adopted."""
+    import torch
+
+    table, change = series_stats(res, g4, g2, pr, sst, tisr, stream=stream)
+    if stream is not None:
+        stream.synchronize()
+    else:
+        torch.cuda.current_stream().synchronize()
+    ms = table.cpu().numpy()
+    sst_change = change.cpu().numpy()
+    bad = [int(i) for i in range(res.nlocal) if res.sst[i] and not sst_change[i]]
+    if bad:
+        raise ValueError(f"local regions {bad} (ids {[int(res.region_ids[i]) for i in bad]}) have the sst flag "
+                         "but an sst series that does not vary (sst_change 0)")
+    if adopt:
+        check(lib().sml_res_set_mean_std_device(res.handle, ptr(table), stream_ptr(stream)))
+    return ms[:, :36].copy(), ms[:, 36:].copy(), sst_change
+
+
+def tile_series(res, g4, g2, pr, sst=None, tisr=None, fc4=None, fc2=None, inputs=None, model=None,
+                in_stride: int | None = None, model_stride: int | None = None, stream=None):
+    """sml_res_tile_series: the T standardised input blocks of a series (and, with fc4
+    [T, 8, 48, 96, 4] / fc2 [T, 48, 96], its T model blocks [nlocal, ncs]) in one launch
+    each, with the context's mean / std.  inputs / model: flat float64 device tensors
+    holding T blocks of in_stride / model_stride doubles (the packed sizes unless
+    given); allocated when None.  sst / tisr None: those entries are not written.
+    Returns (inputs, model)."""
+    import torch
+
+    T, s4, s2 = _truth_series(g4, g2, pr, sst, tisr)
+    tot, nmod = int(res.fb_offsets[-1]), res.nlocal * res.ncs
+    in_stride = tot if in_stride is None else int(in_stride)
+    model_stride = nmod if model_stride is None else int(model_stride)
+    if inputs is None:
+        inputs = torch.zeros(T * in_stride, dtype=torch.float64, device=g4.device)
+    if inputs.numel() < (T - 1) * in_stride + tot:
+        raise ValueError("inputs holds fewer than T blocks of in_stride doubles")
+    f4s = f2s = 0
+    if (fc4 is None) != (fc2 is None):
+        raise ValueError("fc4 and fc2 are given together")
+    if fc4 is not None:
+        Tf, f4s = _series(fc4, "fc4", G4_SHAPE)
+        Tg, f2s = _series(fc2, "fc2", G2_SHAPE)
+        if Tf != T or Tg != T:
+            raise ValueError(f"fc4 / fc2: {Tf} / {Tg} steps, the truth has {T}")
+        if model is None:
+            model = torch.zeros(T * model_stride, dtype=torch.float64, device=g4.device)
+        if model.numel() < (T - 1) * model_stride + nmod:
+            raise ValueError("model holds fewer than T blocks of model_stride doubles")
+    elif model is not None:
+        raise ValueError("model without fc4 / fc2")
+    check(lib().sml_res_tile_series(res.handle, ptr(g4), s4, ptr(g2), ptr(pr), ptr(sst), ptr(tisr), s2, ptr(fc4), f4s,
+                                    ptr(fc2), f2s, T, ptr(inputs), in_stride, ptr(model), model_stride,
+                                    stream_ptr(stream)))
+    return inputs, model
+
+
+def train_from_grids(res, truth, model, discard: int, batch: int, nbatches: int, ncs: int = 132,
+                     beta_res: float = 0.001, beta_model: float = 1.0, using_prior: bool = True,
+                     prior_val: float = 0.0, dtype=np.float32, stream=None):
+    """From a series of global grids to W_out, on the device.  truth = (g4, g2, pr, sst,
+    tisr): the training series, g4 [T, 8, 48, 96, 4], the others [T, 48, 96] (sst None on a
+    context without sst regions, tisr None to leave the tisr entries zero); model =
+    (fc4, fc2), the SPEEDY forecasts of the same steps, or None when ncs == 0;
+    T >= discard + batch * nbatches.
+
+    fit_standardisation over the whole series, adopted; then train_wout's loop, with the
+    blocks it reads tiled `batch` steps at a time into one reused buffer (tile_series):
+    the series is never tiled as a whole.  Returns (wouts, info, mean, std): train_wout's
+    results and the adopted statistics [nlocal, 36]."""
+    import torch
+
+    if ncs != res.ncs:
+        raise ValueError(f"ncs {ncs} differs from the context's chunk_speedy {res.ncs}")
+    if batch < 1:
+        raise ValueError("batch must be >= 1")
+    g4, g2, pr, sst, tisr = truth
+    if ncs and model is None:
+        raise ValueError("model: a hybrid context needs the forecast series")
+    fc4, fc2 = model if ncs else (None, None)
+    T = int(g4.shape[0])
+    if T < discard + batch * nbatches:
+        raise ValueError("the series holds fewer than discard + batch * nbatches steps")
+    mean, std, _ = fit_standardisation(res, g4, g2, pr, sst, tisr, adopt=True, stream=stream)
+    tot, nmod = int(res.fb_offsets[-1]), res.nlocal * ncs
+    d_in = torch.zeros(batch * tot, dtype=torch.float64, device=g4.device)
+    d_mod = torch.zeros(batch * nmod, dtype=torch.float64, device=g4.device) if ncs else None
+
+    def cut(a, t0, m):
+        return None if a is None else a[t0:t0 + m]
+
+    def blocks(t0, m):
+        if m > 0:
+            tile_series(res, cut(g4, t0, m), cut(g2, t0, m), cut(pr, t0, m), cut(sst, t0, m), cut(tisr, t0, m),
+                        cut(fc4, t0, m), cut(fc2, t0, m), inputs=d_in, model=d_mod, stream=stream)
+        return d_in, d_mod
+
+    wouts, info = _fit_wout(res, blocks, batch, discard, batch, nbatches, ncs, beta_res, beta_model, using_prior,
+                            prior_val, dtype, g4.device, stream)
+    return wouts, info, mean, std
