@@ -303,7 +303,8 @@ int sml_res_start_prediction(sml_reservoirs *c, const double *d_inputs, int leng
  * d_states: the layout sml_train_accumulate reads -- regions back to back, region i's
  * block (ncs + n_i) x m column-major, starting at m * sum_{j<i} (ncs + n_j).
  * d_targets: per region nout x m column-major, back to back; NULL skips it; non-NULL
- * on a sml_res_create_generic context (no geometry) is SML_ERR_ARG.
+ * on a sml_res_create_generic context (no geometry) is SML_ERR_ARG until
+ * sml_res_set_target_index has given that context a target table.
  * The discard phase is sml_res_synchronize over the first blocks from x = 0; batch b
  * is then one call on the next m blocks.  Every batch advances from the unsquared
  * state (the reference's ML-only form restarts from the squared column, :1032: a
@@ -314,6 +315,16 @@ int sml_res_start_prediction(sml_reservoirs *c, const double *d_inputs, int leng
  * device's LDS per workgroup, m launches of the update. */
 int sml_res_train_drive(sml_reservoirs *c, const double *d_inputs, int m, int64_t stride, const double *d_model,
                         int64_t model_stride, double *d_states, double *d_targets, void *stream);
+/* the targets of a sml_res_create_generic context (the slab-ocean reservoir): idx
+ * [nlocal][nout] host ints, idx[i][o] the 0-based position in local region i's feedback
+ * of target o.  Afterwards sml_res_train_drive accepts d_targets on that context and
+ * writes u_c[idx] per column through both drive forms; the state columns and the final
+ * state do not depend on whether targets are written.  Every index is checked before
+ * anything changes; the upload waits for the device.  SML_ERR_ARG: a NULL argument; a
+ * context with a geometry (its own table stays the only one); a context with members > 1;
+ * an index outside [0, ninp[i]).  SML_ERR_STATE inside a begun step.  The slab's
+ * positions: sml_slab_target_index. */
+int sml_res_set_target_index(sml_reservoirs *c, const int32_t *idx);
 /* host convenience: H2D, step, D2H (synchronous) */
 int sml_res_step_host(sml_reservoirs *c, const double *feedback, const double *local_model, double *outvec);
 /* bytes of weights + state resident on the device (for roofline bookkeeping) */
@@ -817,6 +828,41 @@ int sml_res_tile_series(sml_reservoirs *c, const double *d_g4, int64_t g4_stride
                         const double *d_pr, const double *d_sst, const double *d_tisr, int64_t g2_stride,
                         const double *d_fc4, int64_t fc4_stride, const double *d_fc2, int64_t fc2_stride, int T,
                         double *d_inputs, int64_t in_stride, double *d_model, int64_t model_stride, void *stream);
+/* The slab-ocean reservoirs' training inputs from the same series (train_slab_ocean_model's
+ * get_training_data_from_atmo, mod_slab_ocean_reservoir.f90:272-376, with
+ * rolling_average_over_a_period_2d, mod_utilities.f90:1766-1804).  `slab` is the generic
+ * context of the local sst regions of `atmo` (the pair sml_hybrid_set_slab takes).  For slab
+ * reservoir s and its feedback entry e (7 * in2d entries: the lowest level's 4 variables,
+ * logp, sst, tisr over the input tile), z_t[e] is the value sml_res_tile_series writes for
+ * the atmo feedback entry atmo_training_data_idx[e] of step t (t = x - mean; t / std with
+ * atmo's adopted mean / std), and column t of the output is
+ *     a_t[e] = (z_lo[e] + z_lo+1[e] + ... + z_t[e]) / d,   lo = max(0, t - window + 1),
+ * summed from 0.0 in ascending step order, one fp64 add per term, no FMA; d = the number
+ * of summed terms while t + 1 < window, `divisor` otherwise.  (window, divisor) = (P + 1, P)
+ * is the reference's rolling average of period P, which sums P + 1 columns and divides by
+ * P; (P, P) is the plain mean of P columns, the statistic the loop's ring feeds the slab at
+ * prediction with P = timestep_slab / timestep - 1.  The caller chooses.
+ * Columns t0 .. t0 + ncols - 1 are written, column t at d_out + (t - t0) * out_stride in
+ * the slab's packed feedback layout (sml_res_feedback_offsets of `slab`); the series' steps
+ * max(0, t0 - window + 1) .. t0 + ncols - 1 are read, straight from the grids.  d_tisr NULL:
+ * the tisr entries are 0.  A column range is bit for bit the same columns of the whole
+ * call; no atomics, no waits between blocks: the same bits on any stream, CU mask and
+ * stride.  One launch per 65535 chunks of 64 columns (an LDS ring of the last values per
+ * entry, re-summed in step order for every column).  The index table is built and uploaded at the first
+ * call and is atmo's from then on.  ncols == 0 is a no-op.  Stream-ordered.  Not cheap on
+ * the host: every call reads both contexts through their getters and re-runs the layout
+ * unit's checks of the slab context (all the rank's regions: about the cost of building the
+ * slab tables), so a caller that loops over column ranges should take large ranges.
+ * SML_ERR_ARG with a message, before anything is enqueued: T < 1; window outside
+ * [1, 1024]; divisor < 1; t0 < 0, ncols < 0 or t0 + ncols > T; the series' stride and
+ * alignment rules of sml_res_tile_series; a NULL context, d_g4, d_g2, d_pr, d_sst or d_out;
+ * out_stride below the slab's packed feedback size; an atmo context that is generic or has
+ * members; a slab context that is not the ML-only generic context of atmo's local sst
+ * regions in order with nout = resx * resy and 7 * in2d inputs each. */
+int sml_slab_train_series(sml_reservoirs *atmo, const sml_reservoirs *slab, const double *d_g4, int64_t g4_stride,
+                          const double *d_g2, const double *d_pr, const double *d_sst, const double *d_tisr,
+                          int64_t g2_stride, int T, int window, int divisor, int t0, int ncols, double *d_out,
+                          int64_t out_stride, void *stream);
 /* the loop's main (reservoir + exchange) and side (SPEEDY) streams */
 int sml_hybrid_streams(const sml_hybrid *h, void **main, void **side);
 /* the CU split of the two streams: SPEEDY's CUs [0, speedy_cus) and the reservoir's
@@ -1036,6 +1082,13 @@ int sml_region_geometry(int numregions, int region, int *g);
  * (x, y).  idx holds 34 * resx * resy entries (136 at 1152 regions); *count receives
  * that number.  sst (0 / 1) is the region's flag; its block follows the targets. */
 int sml_region_target_index(int numregions, int region, int sst, int32_t *idx, int *count);
+/* the 0-based positions of the slab-ocean reservoir's training targets inside the slab
+ * feedback of a region [lowest level (4, inx, iny) | logp | sst | tisr]: entry 5 * inx * iny
+ * + the input-tile position of resolved point o -- the sst section's inner tile
+ * (tile_full_input_to_target_data2d_ocean_model, src/res_domain.f90:691-716), in the order
+ * of the slab outvec (x fastest).  idx holds resx * resy entries (4 at 1152 regions);
+ * *count receives that number.  Rows of sml_res_set_target_index's table. */
+int sml_slab_target_index(int numregions, int region, int32_t *idx, int *count);
 /* processor_decomposition (src/res_domain.f90:31-62): 0-based regions of rank irank */
 int sml_processor_decomposition(int numregions, int numprocs, int irank, int *regions, int *count);
 /* the mean / std (36 each) local region i was loaded with (host copies) */

@@ -48,6 +48,20 @@ int slab_sst(sml_slab *s, const double *d_outvec_all, int64_t all_stride, double
              void *stream, int *wrote);
 int slab_ring(sml_slab *s, int64_t t, const double *d_feedback, int64_t fb_stride, void *stream);
 void slab_strides(const sml_slab *s, int64_t *ov_stride, int64_t *all_stride, int64_t *fb_stride);
+// sml_slab_train_series' view of the atmo context: the composed table of the slab series
+// (build_slab_series_tables; built and uploaded at the first call, the atmo context's
+// from then on) and the adopted mean / std [nlocal][72].  `in` describes both contexts
+// (sml_slab_layout.hpp); its checks run at every call.  Refuses a generic atmo context
+// and one with members.
+struct SlabLayoutIn;
+struct SlabSeriesDev {
+    const int32_t *src;
+    const uint8_t *l;
+    const uint16_t *row;
+    const double *meanstd;
+    int tot;
+};
+int res_slab_series(sml_reservoirs *atmo, const SlabLayoutIn &in, SlabSeriesDev *out);
 
 // --------------------------------------------------------------- geometry
 // Restatement of the res_domain.f90 decomposition used by every reservoir of the

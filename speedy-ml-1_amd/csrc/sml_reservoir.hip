@@ -42,6 +42,7 @@
 #include "sml_devmem.hpp"
 #include "sml_internal.hpp"
 #include "sml_reservoir_layout.hpp"
+#include "sml_slab_layout.hpp"
 #include "sml_timeline.hpp"
 
 SML_TL_DEFINE(reservoir)
@@ -180,6 +181,12 @@ struct sml_reservoirs : PoolPlan {
     uint8_t *d_ser_l = nullptr;
     unsigned char *d_ser_sst = nullptr;  // [nlocal] the regions' sst flags
     double *d_ser_work = nullptr;        // SeriesWork: (2 * kSerSplitMax + 1) * kSerPoints doubles
+    // sml_slab_train_series' table over this (atmo) context's sst regions (build_slab_series_tables),
+    // allocated at the first such call: source, slot and local row of every slab feedback entry
+    int32_t *d_sls_src = nullptr;
+    uint8_t *d_sls_l = nullptr;
+    uint16_t *d_sls_row = nullptr;
+    int sls_tot = -1;  // entries; -1: not built
     double *d_io = nullptr;         // staging for sml_res_step_host
     size_t d_io_n = 0;
     StepEvents timers;
@@ -1444,7 +1451,9 @@ extern "C" int sml_res_train_drive(sml_reservoirs *c, const double *d_inputs, in
     SML_REQUIRE(d_states, "null device buffer");
     SML_REQUIRE(c->ncs == 0 || (d_model && model_stride >= (int64_t)c->nlocal * c->ncs),
                 "model_stride smaller than nlocal * chunk_speedy (or d_model null)");
-    SML_REQUIRE(!d_targets || !c->generic, "a generic (slab) context has no target geometry: d_targets must be NULL");
+    // (a generic context has a target table once sml_res_set_target_index has given it one)
+    SML_REQUIRE(!d_targets || !c->generic || c->d_tgt_idx,
+                "a generic (slab) context has no target geometry: d_targets must be NULL");
     if (c->is_begun()) return fail(SML_ERR_STATE, "sml_res_train_drive inside a begun step");
     if (int rc = check_loaded(c)) return rc;
     hipStream_t st = (hipStream_t)stream;
@@ -1481,6 +1490,30 @@ extern "C" int sml_res_train_drive(sml_reservoirs *c, const double *d_inputs, in
         SML_HIP(hipGetLastError());
         return (int)SML_OK;
     });
+}
+
+// the targets of a generic context (the slab: sml_slab_target_index): the table the two
+// drive forms gather u_c[idx] through, which the geometry gives every other context.
+// Every index is checked before anything changes; the upload waits for the device, since
+// a drive in flight may read the table it replaces.
+extern "C" int sml_res_set_target_index(sml_reservoirs *c, const int32_t *idx) {
+    SML_REQUIRE(c != nullptr, "null reservoir context");
+    SML_REQUIRE(idx, "idx is null");
+    SML_REQUIRE(c->generic, "sml_res_set_target_index on a context with a geometry: its table stays the only one");
+    SML_REQUIRE(c->members == 1, "sml_res_set_target_index on a context of %d members", c->members);
+    if (c->is_begun()) return fail(SML_ERR_STATE, "sml_res_set_target_index inside a begun step");
+    for (int i = 0; i < c->nlocal; ++i)
+        for (int o = 0; o < c->nout; ++o) {
+            const int32_t v = idx[(size_t)i * c->nout + o];
+            SML_REQUIRE(v >= 0 && v < c->ninp[i], "target index %d of local region %d, output %d: outside [0, %d)", v, i,
+                        o, c->ninp[i]);
+        }
+    if (!c->nlocal) return SML_OK;
+    if (!c->d_tgt_idx)
+        if (int rc = pool(c, &c->d_tgt_idx, (int64_t)c->nlocal * c->nout)) return rc;
+    SML_HIP(hipDeviceSynchronize());
+    SML_HIP(hipMemcpy(c->d_tgt_idx, idx, (size_t)c->nlocal * c->nout * sizeof(int32_t), hipMemcpyHostToDevice));
+    return SML_OK;
 }
 
 // the spectral radius of every local region's A (k_res_radius): one launch, then
@@ -1796,6 +1829,38 @@ extern "C" int sml_res_tile_series(sml_reservoirs *c, const double *d_g4, int64_
                            T);
     }
     SML_HIP(hipGetLastError());
+    return SML_OK;
+}
+
+// the slab training series' view of the atmo context (sml_internal.hpp)
+int sml::res_slab_series(sml_reservoirs *c, const SlabLayoutIn &in, SlabSeriesDev *out) {
+    SML_REQUIRE(c && out, "null argument");
+    SML_REQUIRE(!c->generic, "the atmo context is generic: a generic (slab) context has no exchange tables");
+    SML_REQUIRE(c->members == 1, "sml_slab_train_series on an atmo context of %d members", c->members);
+    if (c->sls_tot < 0) {
+        const TablesIn tin{c->numregions, c->nlocal, c->ncs, c->nout, c->geom.data(), c->sst.data(), c->ninp.data(),
+                           c->rd.data(), c->tot_fb, nullptr};
+        SeriesTables ser;
+        if (int rc = build_series_tables(tin, &ser)) return rc;
+        SlabSeriesTables t;
+        if (int rc = build_slab_series_tables(in, ser.src.data(), ser.l.data(), (int64_t)ser.src.size(), &t)) return rc;
+        auto mk = [c](auto **d, const auto &v) {
+            const int rc = pool(c, d, (int64_t)v.size());
+            return rc ? rc : upload(*d, v);
+        };
+        int rc;
+        if ((rc = mk(&c->d_sls_src, t.src)) || (rc = mk(&c->d_sls_l, t.l)) || (rc = mk(&c->d_sls_row, t.row))) {
+            c->mem.release(&c->d_sls_src);
+            c->mem.release(&c->d_sls_l);
+            c->mem.release(&c->d_sls_row);
+            return rc;
+        }
+        c->sls_tot = (int)t.src.size();
+    } else {  // the table is the atmo context's alone; the slab context is checked at every call
+        SlabTables tb;
+        if (int rc = build_slab_tables(in, &tb)) return rc;
+    }
+    *out = {c->d_sls_src, c->d_sls_l, c->d_sls_row, c->d_meanstd, c->sls_tot};
     return SML_OK;
 }
 

@@ -17,6 +17,7 @@
 #include "sml_internal.hpp"
 #include "sml_slab.hpp"
 #include "sml_slab_layout.hpp"
+#include "sml_slab_series.hpp"
 
 using namespace sml;
 
@@ -303,6 +304,55 @@ extern "C" int sml_slab_ring(sml_slab *s, int64_t t, const double *d_feedback, i
     SML_REQUIRE(s && d_feedback && t >= 1, "bad argument");
     if (int rc = check_fb_stride(s, fb_stride)) return rc;
     return slab_ring(s, t, d_feedback, fb_stride, stream);
+}
+
+// ---- the slab reservoirs' training inputs (sml_slab_series.hpp): every argument is
+// checked before anything is enqueued -- the scalars first, which need no context
+extern "C" int sml_slab_train_series(sml_reservoirs *atmo, const sml_reservoirs *slab, const double *d_g4,
+                                     int64_t g4_stride, const double *d_g2, const double *d_pr, const double *d_sst,
+                                     const double *d_tisr, int64_t g2_stride, int T, int window, int divisor, int t0,
+                                     int ncols, double *d_out, int64_t out_stride, void *stream) {
+    SML_REQUIRE(T >= 1, "T = %d: a series holds one step at least", T);
+    SML_REQUIRE(window >= 1 && window <= 1024, "window = %d outside [1, 1024]", window);
+    SML_REQUIRE(divisor >= 1, "divisor = %d: at least 1", divisor);
+    SML_REQUIRE(t0 >= 0 && ncols >= 0 && (int64_t)t0 + ncols <= T, "columns t0 = %d, ncols = %d leave the series' %d steps",
+                t0, ncols, T);
+    SML_REQUIRE(g4_stride >= kGrid4d, "g4_stride %lld smaller than the 4-d grid's %d doubles", (long long)g4_stride,
+                kGrid4d);
+    SML_REQUIRE(g2_stride >= kGrid2d, "g2_stride %lld smaller than a 2-d grid's %d doubles", (long long)g2_stride,
+                kGrid2d);
+    SML_REQUIRE(g4_stride % 2 == 0, "g4_stride %lld is odd: every step's 4-d grid must be 16-byte aligned",
+                (long long)g4_stride);
+    SML_REQUIRE(atmo && slab, "null reservoir context");
+    SML_REQUIRE(d_g4 && d_g2 && d_pr && d_sst && d_out, "null argument (d_g4, d_g2, d_pr, d_sst and d_out are needed)");
+    SML_REQUIRE((uintptr_t)d_g4 % 16 == 0, "d_g4 %p is not 16-byte aligned", (const void *)d_g4);
+    // both contexts as the getters report them, for the layout unit's checks
+    int numregions = 0, nlocal = 0, nout = 0, snum = 0, nslab = 0, sncs = 0, snout = 0;
+    if (int rc = sml_res_info(atmo, &numregions, &nlocal, nullptr, &nout, nullptr)) return rc;
+    if (int rc = sml_res_info(slab, &snum, &nslab, &sncs, &snout, nullptr)) return rc;
+    std::vector<int> ids(nlocal), sids(nslab), ninp(nlocal), sninp(nslab);
+    std::vector<int64_t> off(nlocal + 1), soff(nslab + 1);
+    if (int rc = sml_res_info(atmo, nullptr, nullptr, nullptr, nullptr, ids.data())) return rc;
+    if (int rc = sml_res_info(slab, nullptr, nullptr, nullptr, nullptr, sids.data())) return rc;
+    if (int rc = sml_res_feedback_offsets(atmo, off.data())) return rc;
+    if (int rc = sml_res_feedback_offsets(slab, soff.data())) return rc;
+    for (int i = 0; i < nlocal; ++i)
+        if (int rc = sml_res_ninp(atmo, i, &ninp[i])) return rc;
+    for (int j = 0; j < nslab; ++j)
+        if (int rc = sml_res_ninp(slab, j, &sninp[j])) return rc;
+    SlabSeriesDev tb{};
+    if (int rc = res_slab_series(atmo, {numregions, nlocal, nout, ids.data(), ninp.data(), off.data(), snum, nslab, sncs,
+                                        snout, sids.data(), sninp.data(), soff.data()},
+                                 &tb))
+        return rc;
+    SML_REQUIRE(out_stride >= soff[nslab], "out_stride %lld smaller than the slab's packed feedback size %lld",
+                (long long)out_stride, (long long)soff[nslab]);
+    if (ncols == 0 || tb.tot == 0) return SML_OK;
+    const SlabSeriesIn in{d_g4, d_g2, d_pr, d_sst, d_tisr, g4_stride, g2_stride};
+    launch_slab_series(tb.src, tb.l, tb.row, tb.meanstd, in, tb.tot, window, divisor, t0, t0 + ncols, d_out, out_stride,
+                       (hipStream_t)stream);
+    SML_HIP(hipGetLastError());
+    return SML_OK;
 }
 
 extern "C" int sml_slab_buffers(const sml_slab *s, const double **d_sst_grid, int64_t *sst_stride,

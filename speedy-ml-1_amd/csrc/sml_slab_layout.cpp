@@ -65,4 +65,43 @@ int build_slab_tables(const SlabLayoutIn &in, SlabTables *out) {
     return SML_OK;
 }
 
+int build_slab_series_tables(const SlabLayoutIn &in, const int32_t *ser_src, const uint8_t *ser_l, int64_t ser_len,
+                             SlabSeriesTables *out) {
+    SML_REQUIRE(out, "bad argument");
+    *out = SlabSeriesTables();
+    SlabTables tb;
+    if (int rc = build_slab_tables(in, &tb)) return rc;
+    const int64_t tot_fb = in.nlocal ? in.off[in.nlocal] : 0;
+    SML_REQUIRE(ser_len == tot_fb && (tot_fb == 0 || (ser_src && ser_l)),
+                "the series tables hold %lld entries, the atmo feedback %lld", (long long)ser_len, (long long)tot_fb);
+    const size_t n = tb.ring_src.size();
+    out->src.resize(n);
+    out->l.resize(n);
+    out->row.resize(n);
+    size_t e = 0;
+    for (size_t j = 0; j < tb.row.size(); ++j) {
+        const int i = tb.row[j];
+        for (int64_t k = in.soff[j]; k < in.soff[j + 1]; ++k, ++e) {
+            const int32_t a = tb.ring_src[e];
+            SML_REQUIRE(a >= in.off[i] && a < in.off[i + 1], "slab entry %zu leaves its region's feedback", e);
+            out->src[e] = ser_src[a];
+            out->l[e] = ser_l[a];
+            out->row[e] = (uint16_t)i;
+        }
+    }
+    SML_REQUIRE(e == n, "the slab feedback holds %zu entries, the atmo subsets %zu", e, n);
+    return SML_OK;
+}
+
 }  // namespace sml
+
+// the slab's training targets inside the slab feedback of a region (slab_target_index,
+// sml_slab_layout.hpp): idx holds resx * resy entries, 4 at 1152 regions
+extern "C" int sml_slab_target_index(int numregions, int region, int32_t *idx, int *count) {
+    SML_REQUIRE(idx && count, "null argument");
+    sml::RegionGeom r;
+    SML_REQUIRE(sml::region_geom(numregions, region, &r), "region %d of %d does not decompose the grid", region,
+                numregions);
+    *count = sml::slab_target_index(r, idx);
+    return SML_OK;
+}

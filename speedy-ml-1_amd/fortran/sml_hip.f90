@@ -866,6 +866,36 @@ module sml_hip
       integer(c_int), value :: t
       integer(c_int) :: rc
     end function
+    !> the slab-ocean reservoirs' training inputs from the same series (get_training_data_from_atmo,
+    !> mod_slab_ocean_reservoir.f90:272-376): columns t0 .. t0 + ncols - 1 of the rolling mean
+    !> over `window` steps divided by `divisor` (rolling_average_over_a_period_2d of period P is
+    !> (P + 1, P); the plain mean of P columns is (P, P)), out_stride apart, in the slab
+    !> context's packed feedback layout; d_tisr may be c_null_ptr
+    function sml_slab_train_series(atmo, slab, d_g4, g4_stride, d_g2, d_pr, d_sst, d_tisr, g2_stride, t, window, &
+        divisor, t0, ncols, d_out, out_stride, stream) bind(C, name='sml_slab_train_series') result(rc)
+      import :: c_ptr, c_int, c_int64_t
+      type(c_ptr), value :: atmo, slab, d_g4, d_g2, d_pr, d_sst, d_tisr, d_out, stream
+      integer(c_int64_t), value :: g4_stride, g2_stride, out_stride
+      integer(c_int), value :: t, window, divisor, t0, ncols
+      integer(c_int) :: rc
+    end function
+    !> the targets of a sml_res_create_generic context: idx(nout, nlocal), 0-based positions in
+    !> each local region's feedback; sml_res_train_drive then accepts d_targets on it
+    function sml_res_set_target_index(ctx, idx) bind(C, name='sml_res_set_target_index') result(rc)
+      import :: c_ptr, c_int, c_int32_t
+      type(c_ptr), value :: ctx
+      integer(c_int32_t), intent(in) :: idx(*)
+      integer(c_int) :: rc
+    end function
+    !> the slab reservoir's target positions in its feedback: 5 inx iny + the inner tile's
+    !> points (tile_full_input_to_target_data2d_ocean_model, res_domain.f90:691-716); resx resy entries
+    function sml_slab_target_index(numregions, region, idx, count) bind(C, name='sml_slab_target_index') result(rc)
+      import :: c_int, c_int32_t
+      integer(c_int), value :: numregions, region
+      integer(c_int32_t), intent(out) :: idx(*)
+      integer(c_int), intent(out) :: count
+      integer(c_int) :: rc
+    end function
     !> the spectral radius of every local region's A (gen_res's sparse_eigen,
     !> mod_reservoir.f90:190): lo <= rho <= hi per region, info 0 when hi - lo <= tol * hi;
     !> host arrays of nlocal, filled when the call returns

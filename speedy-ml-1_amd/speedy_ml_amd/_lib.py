@@ -75,6 +75,7 @@ EXPORTED = (
     "sml_ens_create", "sml_ens_destroy", "sml_ens_info", "sml_ens_reset", "sml_ens_moments", "sml_ens_scores",
     "sml_ens_read", "sml_ens_weights",
     "sml_res_series_stats", "sml_res_set_mean_std_device", "sml_res_tile_series",
+    "sml_slab_train_series", "sml_res_set_target_index", "sml_slab_target_index",
 )
 
 SML_HOP_AUTO, SML_HOP_WAIT_VALUE, SML_HOP_EVENTS, SML_HOP_KERNEL = 0, 1, 2, 3
@@ -317,6 +318,9 @@ def _declare(L: ctypes.CDLL) -> None:
         "sml_res_series_stats": [vp, vp, i64, vp, vp, vp, vp, i64, i, vp, vp, vp],
         "sml_res_set_mean_std_device": [vp, vp, vp],
         "sml_res_tile_series": [vp, vp, i64, vp, vp, vp, vp, i64, vp, i64, vp, i64, i, vp, i64, vp, i64, vp],
+        "sml_slab_train_series": [vp, vp, vp, i64, vp, vp, vp, vp, i64, i, i, i, i, i, vp, i64, vp],
+        "sml_res_set_target_index": [vp, vp],
+        "sml_slab_target_index": [i, i, vp, ip],
     }
     for name, args in sig.items():
         if os.environ.get("SML_LIB") and not hasattr(L, name):

@@ -380,6 +380,23 @@ class Reservoirs:
                                             ctypes.byref(cnt)))
         return idx[:cnt.value]
 
+    def slab_target_index(self, i: int) -> np.ndarray:
+        """0-based positions of the slab-ocean reservoir's targets inside the slab feedback
+        of local region i (sml_slab_target_index): the sst section's inner tile."""
+        idx = np.zeros(96 * 48 // self.numregions, dtype=np.int32)
+        cnt = ctypes.c_int()
+        check(lib().sml_slab_target_index(self.numregions, int(self.region_ids[i]), ptr(idx), ctypes.byref(cnt)))
+        return idx[:cnt.value]
+
+    def set_target_index(self, idx):
+        """Give a generic context its training targets (sml_res_set_target_index): idx
+        [nlocal, nout], positions in each local region's feedback; train_drive then
+        accepts d_targets on it."""
+        idx = np.ascontiguousarray(idx, dtype=np.int32)
+        if idx.shape != (self.nlocal, self.nout):
+            raise ValueError(f"idx: shape ({self.nlocal}, {self.nout}) expected, got {idx.shape}")
+        check(lib().sml_res_set_target_index(self._h, ptr(idx)))
+
     def train_drive(self, d_inputs, m: int, d_model, d_states, d_targets=None, stride: int | None = None,
                     model_stride: int | None = None, stream=None):
         """The training drive (sml_res_train_drive; reservoir_layer_chunking_hybrid,

@@ -14,7 +14,8 @@ tensors packing the regions back to back.
 The front end (get_training_data: the standardisation statistics and the tiling of the
 truth and the SPEEDY forecasts) runs on the device too, from a series of global grids:
 fit_standardisation, tile_series, train_from_grids (sml_res_series_stats,
-sml_res_set_mean_std_device, sml_res_tile_series).
+sml_res_set_mean_std_device, sml_res_tile_series).  The slab-ocean reservoirs train from the
+same grids: slab_series, train_slab_from_grids (sml_slab_train_series, sml_res_set_target_index).
 """
 from __future__ import annotations
 
@@ -322,4 +323,127 @@ def train_from_grids(res, truth, model, discard: int, batch: int, nbatches: int,
 
     wouts, info = _fit_wout(res, blocks, batch, discard, batch, nbatches, ncs, beta_res, beta_model, using_prior,
                             prior_val, dtype, g4.device, stream)
+    return wouts, info, mean, std
+
+
+# ---- the slab-ocean reservoirs (sml_slab_train_series, sml_res_set_target_index)
+SLAB_BETA_RES = 0.0001  # initialize_slab_ocean_model: reservoir%beta_res (mod_slab_ocean_reservoir.f90:32)
+
+
+def _own_slabs(atmo, slab):
+    """The local atmo rows of the slab reservoirs; ValueError on a slab context that is not
+    the generic ML-only context of atmo's local sst regions, in order."""
+    rows = [i for i in range(atmo.nlocal) if atmo.sst[i]]
+    ids = [int(atmo.region_ids[i]) for i in rows]
+    if slab.numregions != atmo.numregions or slab.ncs != 0 or [int(r) for r in slab.region_ids] != ids:
+        raise ValueError("slab: not the ML-only context of the atmo context's local sst regions, in order "
+                         f"({len(ids)} sst regions, {slab.nlocal} slab reservoirs)")
+    return rows
+
+
+def slab_series(atmo, slab, g4, g2, pr, sst, tisr=None, window: int = 1, divisor: int = 1, t0: int = 0,
+                ncols: int | None = None, out=None, out_stride: int | None = None, stream=None):
+    """sml_slab_train_series: columns t0 .. t0 + ncols - 1 (all from t0 when ncols is None) of
+    the slab reservoirs' averaged input series, from the grids of a training series (g4
+    [T, 8, 48, 96, 4]; g2 / pr / sst / tisr [T, 48, 96]) with atmo's adopted mean / std:
+    column t = (z_lo + ... + z_t) / d over the last `window` standardised steps, d the
+    number of terms while t + 1 < window, `divisor` afterwards.  (window, divisor) =
+    (P + 1, P) is the reference's rolling_average_over_a_period_2d of period P; (P, P) the
+    plain mean of P columns, what the loop's ring feeds the slab at prediction.  out: a flat
+    float64 device tensor of ncols columns out_stride doubles apart (the slab's packed
+    feedback size unless given); allocated (not filled: with a padded out_stride the words
+    between the columns hold anything) when None.  Stream-ordered.  Returns out."""
+    import torch
+
+    T, s4, s2 = _truth_series(g4, g2, pr, sst, tisr)
+    if sst is None:
+        raise ValueError("sst: the slab series needs the sst series")
+    ncols = T - t0 if ncols is None else int(ncols)
+    tot = int(slab.fb_offsets[-1])
+    out_stride = tot if out_stride is None else int(out_stride)
+    if out is None:
+        # not filled: the kernel writes every word of a column's packed feedback, and a fill on
+        # torch's current stream would not be ordered against a kernel on `stream` (one double
+        # at least: an empty tensor has no address to pass)
+        out = torch.empty(max(ncols * out_stride, 1), dtype=torch.float64, device=g4.device)[:max(ncols, 0) * out_stride]
+    if ncols > 0 and out.numel() < (ncols - 1) * out_stride + tot:
+        raise ValueError("out holds fewer than ncols columns of out_stride doubles")
+    check(lib().sml_slab_train_series(atmo.handle, slab.handle, ptr(g4), s4, ptr(g2), ptr(pr), ptr(sst), ptr(tisr), s2,
+                                      T, int(window), int(divisor), int(t0), ncols,
+                                      ctypes.c_void_p(out.untyped_storage().data_ptr() + 8 * out.storage_offset()), out_stride,
+                                      stream_ptr(stream)))
+    return out
+
+
+def train_slab_from_grids(atmo, slab, truth, window: int, divisor: int, phase_stride: int, discard_cols: int,
+                          batch: int, nbatches: int, beta_res: float = SLAB_BETA_RES, dtype=np.float32,
+                          fit_stats: bool = False, stream=None):
+    """From the grids of a training period to the slab-ocean reservoirs' W_out, on the device:
+    train_slab_ocean_model with get_training_data_from_atmo, reservoir_layer_chunking_ml,
+    chunking_matmul_ml and fit_chunk_ml (mod_slab_ocean_reservoir.f90:173-270, 272-376,
+    802-887, 1353-1397, 994-1050).
+
+    atmo: the atmospheric context with its standardisation adopted -- fit_standardisation is
+    the caller's step (train_from_grids does it); fit_stats=True does it here, over `truth`.
+    slab: the generic context of atmo's local sst regions (A and W_in loaded).  truth =
+    (g4, g2, pr, sst, tisr) as train_from_grids takes it.
+
+    The averaged series (slab_series with (window, divisor)) is made once for all T steps:
+    T * the slab's packed feedback doubles, 0.91 MB a step at full size (1027 reservoirs).
+    The slab gets its target index (Reservoirs.set_target_index of slab_target_index).
+    Then, for each phase i = 0 .. phase_stride - 1 -- the reference's do i = 1, timestep_slab
+    over trainingdata(:, i::timestep_slab) -- on the sub-series i, i + S, i + 2 S, ...:
+    states to zero, Reservoirs.synchronize over discard_cols columns, nbatches times
+    train_drive + Trainer.accumulate into the same sums across the phases.  One
+    Trainer.solve(ncs=0, beta_res) with beta_res on the whole diagonal (fit_chunk_ml)
+    closes; the default beta_res is the reference's for the slab (SLAB_BETA_RES).  The
+    series is used as given: the reference's input noise is the caller's.  Every launch goes
+    to `stream`; the states' reset of each phase is a host copy, so the host waits for
+    `stream` before it (the previous phase's last drive writes the state it zeroes).  A slab
+    context without reservoirs (a rank with no sst region) returns empty results at once.
+
+    Returns (wouts, info, mean, std): per slab reservoir W_out (n, nout), ready for
+    write_region_netcdf / Reservoirs.load_region, the potrf info, and the [nslab, 36] mean /
+    std rows the slab's file carries -- its atmo region's adopted statistics, of which the
+    slab reads the sst slot (35).  ValueError when T < phase_stride * (discard_cols + batch *
+    nbatches) and on a slab context that does not belong to atmo."""
+    import torch
+
+    rows = _own_slabs(atmo, slab)
+    g4, g2, pr, sst, tisr = truth
+    S = int(phase_stride)
+    if S < 1 or batch < 1 or nbatches < 1 or discard_cols < 0:
+        raise ValueError("phase_stride, batch, nbatches must be >= 1 and discard_cols >= 0")
+    T = int(g4.shape[0])
+    if T < S * (discard_cols + batch * nbatches):
+        raise ValueError("the series holds fewer than phase_stride * (discard_cols + batch * nbatches) steps")
+    if fit_stats:
+        fit_standardisation(atmo, g4, g2, pr, sst, tisr, adopt=True, stream=stream)
+    if slab.nlocal == 0:
+        return [], np.zeros(0, dtype=np.int32), np.zeros((0, 36)), np.zeros((0, 36))
+    mean, std = np.zeros((len(rows), 36)), np.zeros((len(rows), 36))
+    for j, i in enumerate(rows):
+        check(lib().sml_res_mean_std(atmo.handle, i, ptr(mean[j]), ptr(std[j])))
+    series = slab_series(atmo, slab, g4, g2, pr, sst, tisr, window, divisor, stream=stream)
+    slab.set_target_index(np.stack([slab.slab_target_index(j) for j in range(slab.nlocal)]))
+    tot = int(slab.fb_offsets[-1])
+    naug = [int(n) for n in slab.n]
+    tr = Trainer(naug, slab.nout)
+    tr.reset(stream=stream)
+    states = torch.empty(sum(naug) * batch, dtype=torch.float64, device=g4.device)
+    targets = torch.empty(len(naug) * batch * slab.nout, dtype=torch.float64, device=g4.device)
+    for i in range(S):
+        # set_state copies from the host with no regard for `stream`, whose last drive (record,
+        # then advance) still writes the state being zeroed: wait for it first
+        (stream if stream is not None else torch.cuda.current_stream()).synchronize()
+        for j, n in enumerate(slab.n):
+            slab.set_state(j, np.zeros(int(n)))
+        slab.synchronize(series[i * tot:], discard_cols, stride=S * tot, stream=stream)
+        for b in range(nbatches):
+            col = i + (discard_cols + b * batch) * S
+            slab.train_drive(series[col * tot:], batch, None, states, targets, stride=S * tot, stream=stream)
+            tr.accumulate(states, targets, batch, stream=stream)
+    packed, info = tr.solve(ncs=0, beta_res=beta_res, using_prior=False, stream=stream)
+    wouts = [v.cpu().numpy().astype(dtype) for v in tr.wout_views(packed)]
+    tr.close()
     return wouts, info, mean, std
