@@ -325,6 +325,44 @@ int sml_res_train_drive(sml_reservoirs *c, const double *d_inputs, int m, int64_
  * an index outside [0, ninp[i]).  SML_ERR_STATE inside a begun step.  The slab's
  * positions: sml_slab_target_index. */
 int sml_res_set_target_index(sml_reservoirs *c, const int32_t *idx);
+/* sml_res_train_drive with the targets of column c read from d_target_inputs +
+ * c * target_stride (the packed feedback layout, target_stride >= total feedback; global
+ * memory) while the states are driven by d_inputs: the clean series beside the noised one
+ * (sml_res_input_noise).  Both drive forms serve it.  With d_target_inputs == d_inputs
+ * and equal strides every output is bit for bit sml_res_train_drive's.  d_target_inputs
+ * is not read (and may be NULL) when d_targets is NULL. */
+int sml_res_train_drive_from(sml_reservoirs *c, const double *d_inputs, int m, int64_t stride,
+                             const double *d_target_inputs, int64_t target_stride, const double *d_model,
+                             int64_t model_stride, double *d_states, double *d_targets, void *stream);
+/* The reference's input noise (gaussian_noise_1d_function, gaussian_noise_1d_function_precip:
+ * src/mod_utilities.f90:1380-1456), reproducible: DESIGN.md §3.11.  Entry e (0-based, within
+ * its region's feedback) of the block of absolute step t draws, with the generator of
+ * sml_gen_region keyed by (seed, the region's noise id),
+ *   b1 = draw(stream 4, (t << 20) | e) >> 11,  u1 = (b1 + 1) 2^-53 in (0, 1]
+ *   b2 = draw(stream 5, (t << 20) | e) >> 11,  u2 = b2 2^-53 in [0, 1)
+ *   g  = sqrt(-2 log(u1)) cospi(2 u2)
+ * and becomes x + (g * noisemag) * x; a precipitation entry (slot 34), when precip_epsilon
+ * > 0 and the context has a geometry, becomes instead, with its region's adopted mean / std,
+ *   p = eps (exp(x std + mean) - 1);  p = |p + g noisemag|;  (log(1 + p / eps) - mean) / std.
+ * noisemag == 0 copies x (a -0.0 keeps its sign).  One rounding per operation.
+ * sml_res_set_input_noise stores the configuration.  ids: host [nlocal] noise ids (>= 0),
+ * or NULL: the context's region ids (the local index on a sml_res_create_generic context),
+ * so a rank's share of the regions draws what a context of all regions draws.  SML_ERR_ARG: a
+ * negative or non-finite noisemag or precip_epsilon, a NULL context, members > 1, a negative
+ * id, a region with ninp >= 2^20.  SML_ERR_STATE inside a begun step.  A context that never
+ * calls it allocates and launches nothing new.
+ * sml_res_input_noise writes blocks t0 .. t0 + m - 1, block j read at d_in + j * in_stride
+ * and written at d_out + j * out_stride (both strides >= total feedback; d_out == d_in with
+ * equal strides is allowed).  d_in == NULL writes g itself for every entry.  One launch,
+ * stream-ordered, no host synchronisation; m == 0 is a no-op.  SML_ERR_ARG: m < 0, steps
+ * outside [0, 2^43), a short stride, a NULL d_out; SML_ERR_STATE before the setter. */
+int sml_res_set_input_noise(sml_reservoirs *c, double noisemag, uint64_t seed, double precip_epsilon,
+                            const int32_t *ids);
+int sml_res_input_noise(sml_reservoirs *c, const double *d_in, int64_t in_stride, double *d_out, int64_t out_stride,
+                        int64_t t0, int m, void *stream);
+/* the two 53-bit integers b1, b2 above, on the host (no device is touched): the device's
+ * own functions.  SML_ERR_ARG: region < 0, t outside [0, 2^43), e outside [0, 2^20), NULL. */
+int sml_noise_bits(uint64_t seed, int region, int64_t t, int64_t e, uint64_t *b1, uint64_t *b2);
 /* host convenience: H2D, step, D2H (synchronous) */
 int sml_res_step_host(sml_reservoirs *c, const double *feedback, const double *local_model, double *outvec);
 /* bytes of weights + state resident on the device (for roofline bookkeeping) */

@@ -5,7 +5,8 @@
 // (src/mod_utilities.f90:1562-1589), the W_in fill of train_reservoir
 // (src/mod_reservoir.f90:260-278).  The reference draws from RANDOM_NUMBER seeded by
 // system_clock, so its matrices were never reproducible; here every number is a pure
-// function of (seed, region, stream, index):
+// function of (seed, region, stream, index) -- the generator of sml_counter_rng.hpp, which
+// the input noise's kernel shares (streams 4 and 5; sml_noise_bits below is its host form):
 //
 //   mix(z):  z ^= z >> 30;  z *= 0xBF58476D1CE4E5B9;
 //            z ^= z >> 27;  z *= 0x94D049BB133111EB;
@@ -33,26 +34,12 @@
 // 2 u - 1 is an odd multiple of 2^-24, never 0.
 #include <vector>
 
+#include "sml_counter_rng.hpp"
 #include "sml_internal.hpp"
 
+using namespace sml;  // mix, stream_key, draw: sml_counter_rng.hpp, shared with the device
+
 namespace {
-
-constexpr uint64_t kGolden = 0x9E3779B97F4A7C15ull;
-
-inline uint64_t mix(uint64_t z) {
-    z ^= z >> 30;
-    z *= 0xBF58476D1CE4E5B9ull;
-    z ^= z >> 27;
-    z *= 0x94D049BB133111EBull;
-    z ^= z >> 31;
-    return z;
-}
-
-inline uint64_t stream_key(uint64_t seed, int region, int stream) {
-    return mix(mix(seed + kGolden) ^ (8ull * (uint64_t)region + (uint64_t)stream));
-}
-
-inline uint64_t draw(uint64_t key, uint64_t index) { return mix(key + (index + 1) * kGolden); }
 
 // out[0 .. count) = the first `count` entries of a shuffle of 1..n, draws first, first + 1, ...
 void shuffle(int n, int count, uint64_t key, uint64_t first, std::vector<int> &choices, int *out) {
@@ -91,5 +78,18 @@ extern "C" int sml_gen_region(int n, int k, int ninp, uint64_t seed, int region,
         win_col[r] = r / q;
         win_val[r] = (float)(sigma * (2.0 * u - 1.0));
     }
+    return SML_OK;
+}
+
+// the two 53-bit integers the input noise draws for step t, entry e of noise region `region`
+// (sml_res_input_noise): host only, the device's own functions
+extern "C" int sml_noise_bits(uint64_t seed, int region, int64_t t, int64_t e, uint64_t *b1, uint64_t *b2) {
+    SML_REQUIRE(region >= 0, "sml_noise_bits: region = %d is negative", region);
+    SML_REQUIRE(b1 && b2, "sml_noise_bits: null output");
+    uint64_t index;
+    SML_REQUIRE(noise_index(t, e, &index), "sml_noise_bits: t = %lld outside [0, 2^43) or e = %lld outside [0, 2^20)",
+                (long long)t, (long long)e);
+    *b1 = noise_bits(stream_key(seed, region, kNoiseStreamU1), index);
+    *b2 = noise_bits(stream_key(seed, region, kNoiseStreamU2), index);
     return SML_OK;
 }

@@ -32,18 +32,23 @@ using namespace sml;
 // A and W_in every column, so it loads them cached (not the update's streaming loads)
 // and streams its columns out instead: 144 full-size regions, 1024 columns 12.8 ms,
 // against 17.3 with the update's hints on the same box (profiles/train_drive.md).
+//
+// The targets of column c are the region's own points of input c: of the driving input
+// (TGT_GLOBAL false: read from its LDS copy), or of a second series tinputs, block c at
+// tinputs + c * tstride (TGT_GLOBAL true, sml_res_train_drive_from: read from global
+// memory) -- the clean series beside a noised driving one (sml_res_input_noise).
 
 // a column is written once and read later by the Gram kernel: streamed past the L2,
 // which the region's A rows are to stay in
 __device__ inline void drive_store(double *p, double v) { __builtin_nontemporal_store(v, p); }
 
-template <typename WT>
+template <typename WT, bool TGT_GLOBAL>
 __global__ __launch_bounds__(kUpdThreads, 4) void k_res_drive(
     const RegionDev *__restrict__ R, const int32_t *__restrict__ row0, const int32_t *__restrict__ a_rp,
     const uint16_t *__restrict__ a_col, const WT *__restrict__ a_val, const int32_t *__restrict__ w_rp,
     const uint16_t *__restrict__ w_col, const WT *__restrict__ w_val, Ell ell, const double *__restrict__ x_old,
-    double *__restrict__ x_new, const double *__restrict__ inputs, int64_t stride, const double *__restrict__ model,
-    int64_t model_stride, const int32_t *__restrict__ tgt_idx, double *__restrict__ states,
+    double *__restrict__ x_new, const double *__restrict__ inputs, int64_t stride,
+    const double *__restrict__ tinputs, int64_t tstride, const double *__restrict__ model, int64_t model_stride, const int32_t *__restrict__ tgt_idx, double *__restrict__ states,
     double *__restrict__ targets, int m, int ncs, int nout, double leak, int lds_x, int lds_u) {
     extern __shared__ __attribute__((aligned(16))) double smem[];
     const int r = blockIdx.x, tid = threadIdx.x;
@@ -53,6 +58,7 @@ __global__ __launch_bounds__(kUpdThreads, 4) void k_res_drive(
                           w_val + rg.w_nz};
     double *sx = smem, *su = smem + 2 * (size_t)lds_x;  // [2][lds_x] states, [2][lds_u] inputs
     const double *u = inputs + rg.fb;
+    const double *tu = TGT_GLOBAL ? tinputs + rg.fb : nullptr;
     RowRegs<WT> cur, nxt;
     load_row<WT, false>(cur, rg, ell, tid, tid < n);
     for (int j = tid; j < n; j += kUpdThreads) sx[j] = x_old[rg.x + j];
@@ -72,8 +78,14 @@ __global__ __launch_bounds__(kUpdThreads, 4) void k_res_drive(
         double uv = 0.0;
         if (more && ureg && tid < ninp) uv = unext[tid];
         for (int j = tid; j < ncs; j += kUpdThreads) drive_store(scol + j, lm[j]);
-        if (tcol)
-            for (int j = tid; j < nout; j += kUpdThreads) drive_store(tcol + j, fs[ti[j]]);
+        if (tcol) {
+            if constexpr (TGT_GLOBAL) {
+                const double *tc = tu + (size_t)c * tstride;
+                for (int j = tid; j < nout; j += kUpdThreads) drive_store(tcol + j, tc[ti[j]]);
+            } else {
+                for (int j = tid; j < nout; j += kUpdThreads) drive_store(tcol + j, fs[ti[j]]);
+            }
+        }
         for (int base = 0; base < n; base += kUpdThreads) {
             const int i = base + tid, inext = i + kUpdThreads;
             if (base + kUpdThreads < n)
@@ -106,10 +118,11 @@ __global__ __launch_bounds__(kUpdThreads, 4) void k_res_drive(
 
 // column c of every region from the state in global memory: the stepwise form of the
 // drive (SML_RES_PATH_STEPWISE_DRIVE, or a region past k_res_drive's LDS), followed by
-// the update's own launch.  grid (nlocal, row chunks of 256)
+// the update's own launch.  tu: the block the targets are read from (the driving block u,
+// or sml_res_train_drive_from's).  grid (nlocal, row chunks of 256)
 __global__ __launch_bounds__(256) void k_drive_record(const RegionDev *__restrict__ R,
                                                       const int32_t *__restrict__ row0,
-                                                      const double *__restrict__ x, const double *__restrict__ u,
+                                                      const double *__restrict__ x, const double *__restrict__ tu,
                                                       const double *__restrict__ lm,
                                                       const int32_t *__restrict__ tgt_idx,
                                                       double *__restrict__ states, double *__restrict__ targets,
@@ -127,7 +140,7 @@ __global__ __launch_bounds__(256) void k_drive_record(const RegionDev *__restric
     }
     if (targets && blockIdx.y == 0) {
         double *tcol = targets + ((int64_t)m * r + c) * nout;
-        for (int t = threadIdx.x; t < nout; t += blockDim.x) tcol[t] = u[rg.fb + tgt_idx[(size_t)r * nout + t]];
+        for (int t = threadIdx.x; t < nout; t += blockDim.x) tcol[t] = tu[rg.fb + tgt_idx[(size_t)r * nout + t]];
     }
 }
 

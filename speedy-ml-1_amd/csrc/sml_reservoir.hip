@@ -39,6 +39,7 @@
 #include <type_traits>
 #include <vector>
 
+#include "sml_counter_rng.hpp"
 #include "sml_devmem.hpp"
 #include "sml_internal.hpp"
 #include "sml_reservoir_layout.hpp"
@@ -55,6 +56,7 @@ SML_TL_DEFINE(reservoir)
 #include "sml_res_radius.hpp"
 #include "sml_res_tiling.hpp"
 #include "sml_res_series.hpp"
+#include "sml_res_noise.hpp"
 #include "sml_res_readout.hpp"
 #include "sml_res_members.hpp"
 // clang-format on
@@ -187,6 +189,13 @@ struct sml_reservoirs : PoolPlan {
     uint8_t *d_sls_l = nullptr;
     uint16_t *d_sls_row = nullptr;
     int sls_tot = -1;  // entries; -1: not built
+    // the input noise (sml_res_set_input_noise; nothing of it exists before that call):
+    // the entries' local regions (a generic context's own table; d_fb_reg elsewhere) and
+    // the regions' keys of streams 4 and 5 [nlocal][2]
+    bool noise_set = false;
+    double noise_mag = 0.0, noise_eps = 0.0;
+    uint16_t *d_nz_reg = nullptr;
+    uint64_t *d_nz_key = nullptr;
     double *d_io = nullptr;         // staging for sml_res_step_host
     size_t d_io_n = 0;
     StepEvents timers;
@@ -1441,11 +1450,15 @@ extern "C" int sml_res_dbg_set_finish_tile(sml_reservoirs *c, int tile) {
 
 // the training drive (k_res_drive): "record, then advance" over one batch of m
 // columns for every local region.  Stream-ordered, no host synchronisation.
-extern "C" int sml_res_train_drive(sml_reservoirs *c, const double *d_inputs, int m, int64_t stride,
-                                   const double *d_model, int64_t model_stride, double *d_states,
-                                   double *d_targets, void *stream) {
+// d_tin: the series the targets are read from (sml_res_train_drive_from), or NULL: the
+// driving series' own blocks, as each kernel holds them.
+namespace {
+
+int train_drive(sml_reservoirs *c, const char *what, const double *d_inputs, int m, int64_t stride,
+                const double *d_tin, int64_t tstride, const double *d_model, int64_t model_stride, double *d_states,
+                double *d_targets, void *stream) {
     SML_REQUIRE(c && m >= 0, "bad argument");
-    if (int rc = check_single(c, "sml_res_train_drive")) return rc;
+    if (int rc = check_single(c, what)) return rc;
     if (c->nlocal == 0 || m == 0) return SML_OK;
     SML_REQUIRE(d_inputs && stride >= (int64_t)c->tot_fb, "stride smaller than the packed feedback size");
     SML_REQUIRE(d_states, "null device buffer");
@@ -1454,7 +1467,7 @@ extern "C" int sml_res_train_drive(sml_reservoirs *c, const double *d_inputs, in
     // (a generic context has a target table once sml_res_set_target_index has given it one)
     SML_REQUIRE(!d_targets || !c->generic || c->d_tgt_idx,
                 "a generic (slab) context has no target geometry: d_targets must be NULL");
-    if (c->is_begun()) return fail(SML_ERR_STATE, "sml_res_train_drive inside a begun step");
+    if (c->is_begun()) return fail(SML_ERR_STATE, "%s inside a begun step", what);
     if (int rc = check_loaded(c)) return rc;
     hipStream_t st = (hipStream_t)stream;
     if (c->ncs == 0) {
@@ -1466,9 +1479,10 @@ extern "C" int sml_res_train_drive(sml_reservoirs *c, const double *d_inputs, in
         const int chunks = (c->ncs + c->maxn + 255) / 256;
         for (int t = 0; t < m; ++t) {
             const double *u = d_inputs + (size_t)t * stride;
+            const double *tu = d_tin ? d_tin + (size_t)t * tstride : u;
             if (int rc = c->advance(false, [&](const double *xo, double *xn) {
                     hipLaunchKernelGGL(k_drive_record, dim3(c->nlocal, chunks), dim3(256), 0, st, c->d_rd, c->d_row0,
-                                       xo, u, d_model + (size_t)t * model_stride, c->d_tgt_idx, d_states, d_targets,
+                                       xo, tu, d_model + (size_t)t * model_stride, c->d_tgt_idx, d_states, d_targets,
                                        t, m, c->ncs, c->nout);
                     return launch_update(c, xo, xn, u, st);
                 }))
@@ -1481,15 +1495,48 @@ extern "C" int sml_res_train_drive(sml_reservoirs *c, const double *d_inputs, in
     return c->advance(false, [&](const double *xo, double *xn) {
         with_wt(c, [&](auto tag) {
             using WT = decltype(tag);
-            hipLaunchKernelGGL(k_res_drive<WT>, dim3(c->nlocal), dim3(kUpdThreads), s.lds_drive, st, c->d_rd,
-                               c->d_row0, c->d_a_rp, c->d_a_col, (const WT *)c->d_a_val, c->d_w_rp, c->d_w_col,
-                               (const WT *)c->d_w_val, ell, xo, xn, d_inputs, stride, d_model, model_stride,
-                               c->d_tgt_idx, d_states, d_targets, m, c->ncs, c->nout, c->leakage, s.lds_x,
-                               c->maxninp);
+            auto launch = [&](auto kernel) {
+                hipLaunchKernelGGL(kernel, dim3(c->nlocal), dim3(kUpdThreads), s.lds_drive, st, c->d_rd, c->d_row0,
+                                   c->d_a_rp, c->d_a_col, (const WT *)c->d_a_val, c->d_w_rp, c->d_w_col,
+                                   (const WT *)c->d_w_val, ell, xo, xn, d_inputs, stride, d_tin, tstride, d_model,
+                                   model_stride, c->d_tgt_idx, d_states, d_targets, m, c->ncs, c->nout, c->leakage,
+                                   s.lds_x, c->maxninp);
+            };
+            if (d_tin && d_targets)
+                launch(k_res_drive<WT, true>);
+            else
+                launch(k_res_drive<WT, false>);
         });
         SML_HIP(hipGetLastError());
         return (int)SML_OK;
     });
+}
+
+}  // namespace
+
+extern "C" int sml_res_train_drive(sml_reservoirs *c, const double *d_inputs, int m, int64_t stride,
+                                   const double *d_model, int64_t model_stride, double *d_states,
+                                   double *d_targets, void *stream) {
+    return train_drive(c, "sml_res_train_drive", d_inputs, m, stride, nullptr, 0, d_model, model_stride, d_states,
+                       d_targets, stream);
+}
+
+// sml_res_train_drive with column c's targets read from d_target_inputs + c * target_stride
+// (global memory), the states driven by d_inputs: the clean series beside the noised one
+extern "C" int sml_res_train_drive_from(sml_reservoirs *c, const double *d_inputs, int m, int64_t stride,
+                                        const double *d_target_inputs, int64_t target_stride, const double *d_model,
+                                        int64_t model_stride, double *d_states, double *d_targets, void *stream) {
+    SML_REQUIRE(c && m >= 0, "bad argument");
+    if (c->nlocal && m && d_targets) {
+        SML_REQUIRE(d_target_inputs, "sml_res_train_drive_from: d_target_inputs is null");
+        SML_REQUIRE(target_stride >= (int64_t)c->tot_fb,
+                    "sml_res_train_drive_from: target_stride %lld smaller than the packed feedback size %lld",
+                    (long long)target_stride, (long long)c->tot_fb);
+    } else {
+        d_target_inputs = nullptr;  // nothing reads it
+    }
+    return train_drive(c, "sml_res_train_drive_from", d_inputs, m, stride, d_target_inputs, target_stride, d_model,
+                       model_stride, d_states, d_targets, stream);
 }
 
 // the targets of a generic context (the slab: sml_slab_target_index): the table the two
@@ -1861,6 +1908,81 @@ int sml::res_slab_series(sml_reservoirs *c, const SlabLayoutIn &in, SlabSeriesDe
         if (int rc = build_slab_tables(in, &tb)) return rc;
     }
     *out = {c->d_sls_src, c->d_sls_l, c->d_sls_row, c->d_meanstd, c->sls_tot};
+    return SML_OK;
+}
+
+// ---------------------------------------------------------------- input noise
+// The configuration of sml_res_input_noise.  ids [nlocal] (host) or NULL:
+// the regions' noise ids -- the context's region ids, the local index on a generic context.
+// The tables are the context's from the first call on; a later call replaces their contents
+// after waiting for the device (a launch in flight may read them).
+extern "C" int sml_res_set_input_noise(sml_reservoirs *c, double noisemag, uint64_t seed, double precip_epsilon,
+                                       const int32_t *ids) {
+    SML_REQUIRE(std::isfinite(noisemag) && noisemag >= 0.0, "sml_res_set_input_noise: noisemag = %g is negative or not finite",
+                noisemag);
+    SML_REQUIRE(std::isfinite(precip_epsilon) && precip_epsilon >= 0.0,
+                "sml_res_set_input_noise: precip_epsilon = %g is negative or not finite", precip_epsilon);
+    SML_REQUIRE(c != nullptr, "null reservoir context");
+    SML_REQUIRE(c->members == 1, "sml_res_set_input_noise on a context of %d members", c->members);
+    if (c->is_begun()) return fail(SML_ERR_STATE, "sml_res_set_input_noise inside a begun step");
+    std::vector<uint64_t> key(2 * (size_t)c->nlocal);
+    for (int i = 0; i < c->nlocal; ++i) {
+        const int id = ids ? ids[i] : c->generic ? i : c->region_ids[i];
+        SML_REQUIRE(id >= 0, "sml_res_set_input_noise: noise id %d of local region %d is negative", id, i);
+        SML_REQUIRE(c->ninp[i] < kNoiseEntryMax, "sml_res_set_input_noise: local region %d has ninp = %d >= 2^20", i,
+                    c->ninp[i]);
+        key[2 * i] = stream_key(seed, id, kNoiseStreamU1);
+        key[2 * i + 1] = stream_key(seed, id, kNoiseStreamU2);
+    }
+    if (c->nlocal) {
+        // the precip branch reads the series tables' slots: a context with a geometry only
+        if (precip_epsilon > 0.0 && !c->generic)
+            if (int rc = ensure_series_tables(c)) return rc;
+        if (c->generic && !c->d_nz_reg) {
+            std::vector<uint16_t> reg((size_t)c->tot_fb);
+            for (int i = 0; i < c->nlocal; ++i)
+                for (int j = 0; j < c->ninp[i]; ++j) reg[(size_t)c->rd[i].fb + j] = (uint16_t)i;
+            if (int rc = pool(c, &c->d_nz_reg, (int64_t)reg.size())) return rc;
+            if (int rc = upload(c->d_nz_reg, reg)) return rc;
+        }
+        if (!c->d_nz_key)
+            if (int rc = pool(c, &c->d_nz_key, (int64_t)key.size())) return rc;
+        SML_HIP(hipDeviceSynchronize());
+        if (int rc = upload(c->d_nz_key, key)) return rc;
+    }
+    c->noise_mag = noisemag;
+    c->noise_eps = precip_epsilon;
+    c->noise_set = true;
+    return SML_OK;
+}
+
+// blocks t0 .. t0 + m - 1 of the packed feedback layout, noised (k_input_noise): block j read
+// at d_in + j * in_stride, written at d_out + j * out_stride.  Stream-ordered.
+extern "C" int sml_res_input_noise(sml_reservoirs *c, const double *d_in, int64_t in_stride, double *d_out,
+                                   int64_t out_stride, int64_t t0, int m, void *stream) {
+    SML_REQUIRE(m >= 0, "sml_res_input_noise: m = %d is negative", m);
+    SML_REQUIRE(t0 >= 0 && t0 <= kNoiseStepMax - (int64_t)m, "sml_res_input_noise: steps t0 = %lld .. + %d outside [0, 2^43)",
+                (long long)t0, m);
+    SML_REQUIRE(c != nullptr, "null reservoir context");
+    SML_REQUIRE(c->members == 1, "sml_res_input_noise on a context of %d members", c->members);
+    if (!c->noise_set) return fail(SML_ERR_STATE, "sml_res_input_noise before sml_res_set_input_noise");
+    if (c->nlocal == 0 || c->tot_fb == 0 || m == 0) return SML_OK;
+    SML_REQUIRE(d_out, "sml_res_input_noise: d_out is null");
+    SML_REQUIRE(out_stride >= (int64_t)c->tot_fb, "sml_res_input_noise: out_stride %lld smaller than the packed feedback size %lld",
+                (long long)out_stride, (long long)c->tot_fb);
+    SML_REQUIRE(!d_in || in_stride >= (int64_t)c->tot_fb,
+                "sml_res_input_noise: in_stride %lld smaller than the packed feedback size %lld", (long long)in_stride,
+                (long long)c->tot_fb);
+    SML_REQUIRE(d_in != d_out || in_stride == out_stride, "sml_res_input_noise: in place with two strides");
+    if (d_in == d_out && c->noise_mag == 0.0) return SML_OK;  // the copy of a block onto itself
+    const bool precip = c->noise_eps > 0.0 && !c->generic;
+    const NoiseDev nz{c->generic ? c->d_nz_reg : c->d_fb_reg, c->d_nz_key, precip ? c->d_ser_l : nullptr, c->d_meanstd,
+                      c->noise_mag, c->noise_eps};
+    const int total = (int)c->tot_fb;
+    const int tiles = std::min((m + kTileMem - 1) / kTileMem, 65535);
+    hipLaunchKernelGGL(k_input_noise, dim3((total + kNoiseThreads - 1) / kNoiseThreads, tiles), dim3(kNoiseThreads), 0,
+                       (hipStream_t)stream, c->d_rd, nz, d_in, in_stride, d_out, out_stride, t0, m, total);
+    SML_HIP(hipGetLastError());
     return SML_OK;
 }
 

@@ -887,6 +887,37 @@ module sml_hip
       integer(c_int32_t), intent(in) :: idx(*)
       integer(c_int) :: rc
     end function
+    !> sml_res_train_drive with column c's targets read from d_target_inputs + c * target_stride
+    !> (the clean series) while d_inputs (the noised one) drives the states
+    function sml_res_train_drive_from(ctx, d_inputs, m, stride, d_target_inputs, target_stride, d_model, &
+        model_stride, d_states, d_targets, stream) bind(C, name='sml_res_train_drive_from') result(rc)
+      import :: c_ptr, c_int, c_int64_t
+      type(c_ptr), value :: ctx, d_inputs, d_target_inputs, d_model, d_states, d_targets, stream
+      integer(c_int), value :: m
+      integer(c_int64_t), value :: stride, target_stride, model_stride
+      integer(c_int) :: rc
+    end function
+    !> the reference's input noise (gaussian_noise_1d_function[_precip], mod_utilities.f90:1380-1456),
+    !> reproducible from (seed, noise id, step, entry): the configuration; ids(nlocal) or c_null_ptr
+    !> (the context's region ids).  seed: the 64 bits of the C uint64_t
+    function sml_res_set_input_noise(ctx, noisemag, seed, precip_epsilon, ids) &
+        bind(C, name='sml_res_set_input_noise') result(rc)
+      import :: c_ptr, c_int, c_int64_t, c_double
+      type(c_ptr), value :: ctx, ids
+      real(c_double), value :: noisemag, precip_epsilon
+      integer(c_int64_t), value :: seed
+      integer(c_int) :: rc
+    end function
+    !> blocks t0 .. t0 + m - 1 (absolute 0-based steps) of the packed feedback layout, noised:
+    !> d_out may be d_in; d_in c_null_ptr writes the normal draws themselves
+    function sml_res_input_noise(ctx, d_in, in_stride, d_out, out_stride, t0, m, stream) &
+        bind(C, name='sml_res_input_noise') result(rc)
+      import :: c_ptr, c_int, c_int64_t
+      type(c_ptr), value :: ctx, d_in, d_out, stream
+      integer(c_int64_t), value :: in_stride, out_stride, t0
+      integer(c_int), value :: m
+      integer(c_int) :: rc
+    end function
     !> the slab reservoir's target positions in its feedback: 5 inx iny + the inner tile's
     !> points (tile_full_input_to_target_data2d_ocean_model, res_domain.f90:691-716); resx resy entries
     function sml_slab_target_index(numregions, region, idx, count) bind(C, name='sml_slab_target_index') result(rc)

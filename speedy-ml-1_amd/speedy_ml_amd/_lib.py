@@ -76,6 +76,7 @@ EXPORTED = (
     "sml_ens_read", "sml_ens_weights",
     "sml_res_series_stats", "sml_res_set_mean_std_device", "sml_res_tile_series",
     "sml_slab_train_series", "sml_res_set_target_index", "sml_slab_target_index",
+    "sml_res_train_drive_from", "sml_res_set_input_noise", "sml_res_input_noise", "sml_noise_bits",
 )
 
 SML_HOP_AUTO, SML_HOP_WAIT_VALUE, SML_HOP_EVENTS, SML_HOP_KERNEL = 0, 1, 2, 3
@@ -321,6 +322,10 @@ def _declare(L: ctypes.CDLL) -> None:
         "sml_slab_train_series": [vp, vp, vp, i64, vp, vp, vp, vp, i64, i, i, i, i, i, vp, i64, vp],
         "sml_res_set_target_index": [vp, vp],
         "sml_slab_target_index": [i, i, vp, ip],
+        "sml_res_train_drive_from": [vp, vp, i, i64, vp, i64, vp, i64, vp, vp, vp],
+        "sml_res_set_input_noise": [vp, d, ctypes.c_uint64, d, vp],
+        "sml_res_input_noise": [vp, vp, i64, vp, i64, i64, i, vp],
+        "sml_noise_bits": [ctypes.c_uint64, i, i64, i64, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)],
     }
     for name, args in sig.items():
         if os.environ.get("SML_LIB") and not hasattr(L, name):

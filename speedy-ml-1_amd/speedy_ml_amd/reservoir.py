@@ -397,16 +397,51 @@ class Reservoirs:
             raise ValueError(f"idx: shape ({self.nlocal}, {self.nout}) expected, got {idx.shape}")
         check(lib().sml_res_set_target_index(self._h, ptr(idx)))
 
+    def set_input_noise(self, noisemag: float, seed: int, precip_epsilon: float = 0.0, ids=None):
+        """The configuration of input_noise (sml_res_set_input_noise): the reference's
+        gaussian_noise_1d_function of magnitude noisemag, drawn from (seed, the region's noise
+        id, step, entry); precip_epsilon > 0 turns on gaussian_noise_1d_function_precip's branch
+        for the precipitation entries of a context with a geometry.  ids [nlocal]: the regions'
+        noise ids; None: the region ids (the local index on a generic context)."""
+        if ids is not None:
+            ids = np.ascontiguousarray(ids, dtype=np.int32)
+            if ids.shape != (self.nlocal,):
+                raise ValueError(f"ids: shape ({self.nlocal},) expected, got {ids.shape}")
+        check(lib().sml_res_set_input_noise(self._h, float(noisemag), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                            float(precip_epsilon), ptr(ids)))
+
+    def input_noise(self, d_in, d_out, t0: int, m: int, in_stride: int | None = None, out_stride: int | None = None,
+                    stream=None):
+        """sml_res_input_noise: blocks t0 .. t0 + m - 1 (absolute steps of the series) of
+        d_in, noised, into d_out (flat float64 device tensors of m blocks in_stride /
+        out_stride doubles apart, the packed feedback size unless given; d_out may be d_in).
+        d_in None: the normal draws g themselves.  One launch, stream-ordered.  Returns d_out."""
+        tot = int(self.fb_offsets[-1])
+        in_stride = tot if in_stride is None else int(in_stride)
+        out_stride = tot if out_stride is None else int(out_stride)
+        if m < 0:
+            raise ValueError("m must be >= 0")
+        if m > 0:
+            if d_in is not None and d_in.numel() < (m - 1) * in_stride + tot:
+                raise ValueError("d_in holds fewer than m blocks of in_stride doubles")
+            if d_out.numel() < (m - 1) * out_stride + tot:
+                raise ValueError("d_out holds fewer than m blocks of out_stride doubles")
+        check(lib().sml_res_input_noise(self._h, ptr(d_in), in_stride, ptr(d_out), out_stride, int(t0), int(m),
+                                        stream_ptr(stream)))
+        return d_out
+
     def train_drive(self, d_inputs, m: int, d_model, d_states, d_targets=None, stride: int | None = None,
-                    model_stride: int | None = None, stream=None):
+                    model_stride: int | None = None, stream=None, target_inputs=None,
+                    target_stride: int | None = None):
         """The training drive (sml_res_train_drive; reservoir_layer_chunking_hybrid,
         mod_reservoir.f90:1065-1173): for each of the m input blocks of d_inputs, column c
         of every region's block of d_states = [model block c; the current state with its
         odd nodes squared], column c of d_targets = the region's targets of block c, then
         the state advances on block c.  d_states / d_targets are packed as
         Trainer.accumulate reads them.  d_model: m blocks of [nlocal][ncs] (None when
-        chunk_speedy == 0).  The series is taken as given: input noise
-        (gaussian_noise_1d_function) is the caller's."""
+        chunk_speedy == 0).  target_inputs (sml_res_train_drive_from): a second series, m
+        blocks target_stride apart, the targets are read from instead -- the clean series
+        beside a d_inputs that input_noise has noised, as the reference trains."""
         stride = int(self.fb_offsets[-1]) if stride is None else int(stride)
         model_stride = self.nlocal * self.ncs if model_stride is None else int(model_stride)
         if m < 0:
@@ -420,9 +455,17 @@ class Reservoirs:
                 raise ValueError("d_states is smaller than m * sum(ncs + n)")
             if d_targets is not None and d_targets.numel() < m * self.nlocal * self.nout:
                 raise ValueError("d_targets is smaller than m * nlocal * nout")
-        check(lib().sml_res_train_drive(self._h, ptr(d_inputs), int(m), stride,
-                                        ptr(d_model if self.ncs else None), model_stride, ptr(d_states),
-                                        ptr(d_targets), stream_ptr(stream)))
+        if target_inputs is None:
+            check(lib().sml_res_train_drive(self._h, ptr(d_inputs), int(m), stride,
+                                            ptr(d_model if self.ncs else None), model_stride, ptr(d_states),
+                                            ptr(d_targets), stream_ptr(stream)))
+            return
+        target_stride = int(self.fb_offsets[-1]) if target_stride is None else int(target_stride)
+        if m > 0 and target_inputs.numel() < (m - 1) * target_stride + int(self.fb_offsets[-1]):
+            raise ValueError("target_inputs holds fewer than m blocks of `target_stride` doubles")
+        check(lib().sml_res_train_drive_from(self._h, ptr(d_inputs), int(m), stride, ptr(target_inputs), target_stride,
+                                             ptr(d_model if self.ncs else None), model_stride, ptr(d_states),
+                                             ptr(d_targets), stream_ptr(stream)))
 
     def set_begin_mode(self, mode: int):
         """predict_begin's form: 0 update grid + readout grid, 1 / 2 one fused launch

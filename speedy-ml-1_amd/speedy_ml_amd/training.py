@@ -16,16 +16,34 @@ truth and the SPEEDY forecasts) runs on the device too, from a series of global 
 fit_standardisation, tile_series, train_from_grids (sml_res_series_stats,
 sml_res_set_mean_std_device, sml_res_tile_series).  The slab-ocean reservoirs train from the
 same grids: slab_series, train_slab_from_grids (sml_slab_train_series, sml_res_set_target_index).
+
+The reference never feeds a reservoir the clean input: every W_in product wraps it in
+gaussian_noise_1d_function[_precip] (mod_reservoir.f90:1091-1170), the regulariser of the
+free-running forecast.  noise=InputNoise(...) on train_wout, train_from_grids and
+train_slab_from_grids does the same on the device (Reservoirs.input_noise), reproducibly: the
+discard phase and every batch are driven by the noised blocks, the targets stay clean
+(Reservoirs.train_drive(target_inputs=...)).
 """
 from __future__ import annotations
 
 import ctypes
+from dataclasses import dataclass
 
 import numpy as np
 
 from ._lib import check, lib, ptr, stream_ptr
 
 NOUT = 136
+
+
+@dataclass(frozen=True)
+class InputNoise:
+    """The input noise of a training run (Reservoirs.set_input_noise): the reference's
+    noisemag, the seed every draw is a function of, and model_parameters%precip_epsilon
+    (0: precipitation entries take the plain formula, its precip_bool = .false.)."""
+    noisemag: float
+    seed: int
+    precip_epsilon: float = 0.0
 
 
 class Trainer:
@@ -94,11 +112,14 @@ class Trainer:
 
 
 def _fit_wout(res, blocks, sync_chunk: int, discard: int, batch: int, nbatches: int, ncs: int, beta_res: float,
-              beta_model: float, using_prior: bool, prior_val: float, dtype, device, stream):
+              beta_model: float, using_prior: bool, prior_val: float, dtype, device, stream, noise=None):
     """The loop train_wout and train_from_grids share: states to zero, the discard phase
     (Reservoirs.synchronize over at most sync_chunk blocks a call), per batch one
     Reservoirs.train_drive + Trainer.accumulate, then Trainer.solve.  blocks(t0, m): the
-    packed input blocks t0 .. t0 + m - 1 and their model blocks (None when ncs == 0)."""
+    packed input blocks t0 .. t0 + m - 1 and their model blocks (None when ncs == 0).
+    With noise (an InputNoise), blocks t0 .. t0 + m - 1 are noised with t = t0 .. into one
+    reused buffer (Reservoirs.input_noise) that the discard phase and the drives read; the
+    drives' targets come from the clean blocks."""
     import torch
 
     naug = [ncs + int(n) for n in res.n]
@@ -106,10 +127,16 @@ def _fit_wout(res, blocks, sync_chunk: int, discard: int, batch: int, nbatches: 
         res.set_state(i, np.zeros(int(n)))
     if discard == 0:
         res.synchronize(blocks(0, 0)[0], 0, stream=stream)
+    noisy = None
+    if noise is not None:
+        res.set_input_noise(noise.noisemag, noise.seed, noise.precip_epsilon)
+        tot = int(res.fb_offsets[-1])
+        noisy = torch.empty(max(max(min(sync_chunk, discard), batch) * tot, 1), dtype=torch.float64, device=device)
     t = 0
     while t < discard:
         m = min(sync_chunk, discard - t)
-        res.synchronize(blocks(t, m)[0], m, stream=stream)
+        d_in = blocks(t, m)[0]
+        res.synchronize(d_in if noisy is None else res.input_noise(d_in, noisy, t, m, stream=stream), m, stream=stream)
         t += m
     tr = Trainer(naug, res.nout)
     tr.reset(stream=stream)
@@ -117,7 +144,11 @@ def _fit_wout(res, blocks, sync_chunk: int, discard: int, batch: int, nbatches: 
     targets = torch.empty(len(naug) * batch * res.nout, dtype=torch.float64, device=device)
     for b in range(nbatches):
         d_in, d_mod = blocks(discard + b * batch, batch)
-        res.train_drive(d_in, batch, d_mod if ncs else None, states, targets, stream=stream)
+        if noisy is None:
+            res.train_drive(d_in, batch, d_mod if ncs else None, states, targets, stream=stream)
+        else:
+            res.input_noise(d_in, noisy, discard + b * batch, batch, stream=stream)
+            res.train_drive(noisy, batch, d_mod if ncs else None, states, targets, stream=stream, target_inputs=d_in)
         tr.accumulate(states, targets, batch, stream=stream)
     packed, info = tr.solve(ncs=ncs, beta_res=beta_res, beta_model=beta_model, using_prior=using_prior,
                             prior_val=prior_val, stream=stream)
@@ -128,7 +159,7 @@ def _fit_wout(res, blocks, sync_chunk: int, discard: int, batch: int, nbatches: 
 
 def train_wout(res, d_inputs, d_model, discard: int, batch: int, nbatches: int, ncs: int = 132,
                beta_res: float = 0.001, beta_model: float = 1.0, using_prior: bool = True, prior_val: float = 0.0,
-               dtype=np.float32, stream=None):
+               dtype=np.float32, stream=None, noise=None):
     """Train W_out of every local region of `res` (a Reservoirs with A and W_in loaded:
     genres.generate draws them and scales A to its spectral radius, gen_res + the W_in
     fill of train_reservoir) from a training series on the device: the reference's train_reservoir tail,
@@ -139,8 +170,11 @@ def train_wout(res, d_inputs, d_model, discard: int, batch: int, nbatches: int, 
     d_model:  the same number of (nlocal, ncs) model blocks (None when ncs == 0).
     The states start at zero and run `discard` updates (Reservoirs.synchronize); batch b
     is then one Reservoirs.train_drive over blocks discard + b * batch .. + batch - 1
-    followed by Trainer.accumulate; Trainer.solve closes.  The series is used as given:
-    the reference's input noise (gaussian_noise_1d_function) is the caller's to add.
+    followed by Trainer.accumulate; Trainer.solve closes.  noise=None uses the series as
+    given; noise=InputNoise(noisemag, seed, precip_epsilon) adds the reference's input noise
+    (gaussian_noise_1d_function[_precip]) on the device: block t, noised with step t, drives
+    the discard phase (at most `batch` blocks a call then) and the batches, whose targets
+    stay the clean blocks'.
 
     Returns (wouts, info): per region W_out as a float32 (ncs + n, nout) array -- C order
     of the file's wout(nout, ncs + n), NF90_REAL, ready for write_region_netcdf /
@@ -162,8 +196,8 @@ def train_wout(res, d_inputs, d_model, discard: int, batch: int, nbatches: int, 
     def blocks(t0, m):
         return d_inputs[t0 * tot:], (d_model[t0 * nmod:] if ncs else None)
 
-    return _fit_wout(res, blocks, max(discard, 1), discard, batch, nbatches, ncs, beta_res, beta_model, using_prior,
-                     prior_val, dtype, d_inputs.device, stream)
+    return _fit_wout(res, blocks, max(discard, 1) if noise is None else max(batch, 1), discard, batch, nbatches, ncs,
+                     beta_res, beta_model, using_prior, prior_val, dtype, d_inputs.device, stream, noise=noise)
 
 
 # ---- from a series of global grids (sml_res_series_stats, sml_res_tile_series)
@@ -283,7 +317,7 @@ def tile_series(res, g4, g2, pr, sst=None, tisr=None, fc4=None, fc2=None, inputs
 
 def train_from_grids(res, truth, model, discard: int, batch: int, nbatches: int, ncs: int = 132,
                      beta_res: float = 0.001, beta_model: float = 1.0, using_prior: bool = True,
-                     prior_val: float = 0.0, dtype=np.float32, stream=None):
+                     prior_val: float = 0.0, dtype=np.float32, stream=None, noise=None):
     """From a series of global grids to W_out, on the device.  truth = (g4, g2, pr, sst,
     tisr): the training series, g4 [T, 8, 48, 96, 4], the others [T, 48, 96] (sst None on a
     context without sst regions, tisr None to leave the tisr entries zero); model =
@@ -292,8 +326,10 @@ def train_from_grids(res, truth, model, discard: int, batch: int, nbatches: int,
 
     fit_standardisation over the whole series, adopted; then train_wout's loop, with the
     blocks it reads tiled `batch` steps at a time into one reused buffer (tile_series):
-    the series is never tiled as a whole.  Returns (wouts, info, mean, std): train_wout's
-    results and the adopted statistics [nlocal, 36]."""
+    the series is never tiled as a whole.  noise: as train_wout takes it -- each tiled
+    batch of clean blocks is noised into a second reused buffer with t = the blocks' steps in
+    the series, and its precipitation branch reads the statistics adopted here.  Returns
+    (wouts, info, mean, std): train_wout's results and the adopted statistics [nlocal, 36]."""
     import torch
 
     if ncs != res.ncs:
@@ -322,7 +358,7 @@ def train_from_grids(res, truth, model, discard: int, batch: int, nbatches: int,
         return d_in, d_mod
 
     wouts, info = _fit_wout(res, blocks, batch, discard, batch, nbatches, ncs, beta_res, beta_model, using_prior,
-                            prior_val, dtype, g4.device, stream)
+                            prior_val, dtype, g4.device, stream, noise=noise)
     return wouts, info, mean, std
 
 
@@ -377,7 +413,7 @@ def slab_series(atmo, slab, g4, g2, pr, sst, tisr=None, window: int = 1, divisor
 
 def train_slab_from_grids(atmo, slab, truth, window: int, divisor: int, phase_stride: int, discard_cols: int,
                           batch: int, nbatches: int, beta_res: float = SLAB_BETA_RES, dtype=np.float32,
-                          fit_stats: bool = False, stream=None):
+                          fit_stats: bool = False, stream=None, noise=None):
     """From the grids of a training period to the slab-ocean reservoirs' W_out, on the device:
     train_slab_ocean_model with get_training_data_from_atmo, reservoir_layer_chunking_ml,
     chunking_matmul_ml and fit_chunk_ml (mod_slab_ocean_reservoir.f90:173-270, 272-376,
@@ -396,8 +432,13 @@ def train_slab_from_grids(atmo, slab, truth, window: int, divisor: int, phase_st
     states to zero, Reservoirs.synchronize over discard_cols columns, nbatches times
     train_drive + Trainer.accumulate into the same sums across the phases.  One
     Trainer.solve(ncs=0, beta_res) with beta_res on the whole diagonal (fit_chunk_ml)
-    closes; the default beta_res is the reference's for the slab (SLAB_BETA_RES).  The
-    series is used as given: the reference's input noise is the caller's.  Every launch goes
+    closes; the default beta_res is the reference's for the slab (SLAB_BETA_RES).
+    noise=None uses the series as given.  noise=InputNoise(...) adds the reference's input
+    noise: the averaged series, which exists as a whole, gets a noised copy in one launch
+    (Reservoirs.input_noise with t = the column's index in the series and the atmosphere's
+    global ids of the sst regions as noise ids; every entry plain, the slab context has no
+    geometry); the discard columns and the drives read the copy, the targets the clean
+    series.  Every launch goes
     to `stream`; the states' reset of each phase is a host copy, so the host waits for
     `stream` before it (the previous phase's last drive writes the state it zeroes).  A slab
     context without reservoirs (a rank with no sst region) returns empty results at once.
@@ -427,6 +468,10 @@ def train_slab_from_grids(atmo, slab, truth, window: int, divisor: int, phase_st
     series = slab_series(atmo, slab, g4, g2, pr, sst, tisr, window, divisor, stream=stream)
     slab.set_target_index(np.stack([slab.slab_target_index(j) for j in range(slab.nlocal)]))
     tot = int(slab.fb_offsets[-1])
+    driving = series
+    if noise is not None:
+        slab.set_input_noise(noise.noisemag, noise.seed, noise.precip_epsilon, ids=slab.region_ids)
+        driving = slab.input_noise(series, torch.empty_like(series), 0, T, stream=stream)
     naug = [int(n) for n in slab.n]
     tr = Trainer(naug, slab.nout)
     tr.reset(stream=stream)
@@ -438,10 +483,14 @@ def train_slab_from_grids(atmo, slab, truth, window: int, divisor: int, phase_st
         (stream if stream is not None else torch.cuda.current_stream()).synchronize()
         for j, n in enumerate(slab.n):
             slab.set_state(j, np.zeros(int(n)))
-        slab.synchronize(series[i * tot:], discard_cols, stride=S * tot, stream=stream)
+        slab.synchronize(driving[i * tot:], discard_cols, stride=S * tot, stream=stream)
         for b in range(nbatches):
             col = i + (discard_cols + b * batch) * S
-            slab.train_drive(series[col * tot:], batch, None, states, targets, stride=S * tot, stream=stream)
+            if noise is None:
+                slab.train_drive(series[col * tot:], batch, None, states, targets, stride=S * tot, stream=stream)
+            else:
+                slab.train_drive(driving[col * tot:], batch, None, states, targets, stride=S * tot, stream=stream,
+                                 target_inputs=series[col * tot:], target_stride=S * tot)
             tr.accumulate(states, targets, batch, stream=stream)
     packed, info = tr.solve(ncs=0, beta_res=beta_res, using_prior=False, stream=stream)
     wouts = [v.cpu().numpy().astype(dtype) for v in tr.wout_views(packed)]
